@@ -2,6 +2,7 @@
 """bench.py -- images/sec of the MonoFlex hot path on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode infer|train] [--batch B] [--dtype bf16|fp16|fp32|fp16x2]
+                  [--full] [--dump-outputs DIR]
 
 --mode infer (default; BASELINE configs[1] / C5 with --batch 32): one "step" = DLA-34 + DCNv2 + all heads forward +
     NMS / top-K / 3D decode over one batch of synthetic 1280x384 images already resident in HBM, replayed from one hipGraph.
@@ -11,8 +12,16 @@
     `--batch` images per GPU; N > 1 = data parallel, gradients averaged by an RCCL all-reduce of one flat fp32 buffer
     between the captured forward/backward graph and the captured optimizer graph (engine/trainer.GraphedTrainStep).
 
-The default run (`python bench.py --gpus N`, what the driver records) carries the whole BASELINE.json metric in ONE line: the
-top level is the forward+decode number (bf16, configs[1]); `"train"` is a short graphed run of the training step (fwd + loss +
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it sets up, warms up (inference: at
+least W steps and one second of replays, then one untimed region), times ONE region of exactly K steps, writes the last step's outputs
+when `--dump-outputs DIR` is given, and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the
+timing and the config).
+`--dump-outputs DIR`: what the timed path returned in its last step, as DIR/<name>.npy in float32 (float64 for integer data); the
+inputs are seeded, so two builds compare output for output.
+
+`--full` carries the whole BASELINE.json metric in ONE line: the
+top level is the forward+decode number (bf16, configs[1]) with its roofline objects, its deviation from the reference's goldens and the
+CPU baseline, timed over `--repeats` regions; `"train"` is a short graphed run of the training step (fwd + loss +
 bwd + AdamW, data parallel for N > 1: the metric's "fwd+bwd img/s") with its own roofline object; `"fp32_parity"` is the mode
 that meets the north-star tolerance (<= 1e-3 on logits, identical top-K against the reference's goldens) timed the same way;
 `"fp16x2_parity"` meets the same tolerance on the fp16 matrix pipe (fp32 activations, every MFMA operand an fp16 (hi, lo) pair);
@@ -24,7 +33,8 @@ the reference is 4-8x smaller than bf16's -- the headline stays bf16 because BAS
 `"train_fp16"` is the training step with fp16 activations under the dynamic loss scaler (BASELINE configs[3]'s "fp16 MFMA path";
 `config.loss_scale` / `optimizer_steps_applied` say what the scaler did).
 `--legs none` prints the top level only.  Every timed region is exactly `--steps` steps between barrier + synchronize; it is
-repeated `--repeats` times and the MEDIAN repeat is reported (all repeats are listed in `config.timing`).
+repeated `--repeats` times (default: 1 in a plain run; with `--full` 5 for inference, 3 for training) and the MEDIAN repeat is reported
+(all repeats are listed in `config.timing`).
 
 N > 1 without a torchrun environment: this script re-executes itself under `python -m torch.distributed.run` (one rank
 per GPU, rendezvous on 127.0.0.1), so `python bench.py --gpus 8` is a complete command.  Rank 0 prints ONE JSON line.
@@ -74,7 +84,7 @@ def parse():
     ap.add_argument("--sync-bn", default="auto", choices=["auto", "on", "off"],
                     help="train mode, N > 1: synchronised BatchNorm statistics (the reference trains with USE_SYNC_BN True: runs/monoflex.yaml:59). "
                          "auto = on whenever N > 1; the statistics collectives are captured inside the step's hipGraphs")
-    ap.add_argument("--legs", default="all", choices=["all", "none"], help="infer mode: add the `train` and `fp32_parity` legs to the line")
+    ap.add_argument("--legs", default="all", choices=["all", "none"], help="infer mode with --full: add the `train` and `fp32_parity` legs to the line")
     ap.add_argument("--repeats", type=int, default=None, help="timed regions of exactly --steps steps; the median is reported")
     ap.add_argument("--leg-timeout", type=int, default=420, help="seconds after which unfinished legs are reported as errors and the line is printed")
     ap.add_argument("--train-steps", type=int, default=50, help="timed steps per repeat of the `train` legs (SURVEY 8d: >= 50 timed iterations)")
@@ -83,13 +93,16 @@ def parse():
     ap.add_argument("--train-batches", type=int, default=4, help="distinct synthetic batches rotated through the training step")
     ap.add_argument("--opts", default="", help="library tuning options k=v,... (mfx_set_option), for experiments")
     ap.add_argument("--no-families", action="store_true", help="skip the per-family stage timings (profiling runs: their stand-alone replays would end the trace)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the legs, the roofline objects, the deviation from the "
+                                                        "reference's goldens, the CPU baselines and repeated timed regions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 30 if a.mode == "infer" else 50
     if a.warmup is None:
         a.warmup = 5 if a.mode == "infer" else 10
     if a.repeats is None:
-        a.repeats = 5 if a.mode == "infer" else 3
+        a.repeats = (5 if a.mode == "infer" else 3) if a.full else 1
     return a
 
 
@@ -112,6 +125,33 @@ def timed_repeats(run, steps, repeats, images_per_repeat, device):
         _, dt, n_img = parallel.aggregate_throughput(dt, images_per_repeat, device=device)
         all_s.append(dt)
     return statistics.median(all_s), n_img, all_s
+
+
+WARMUP_S, WARMUP_RUN = 1.0, 50        # warm-up of the inference step before its timed region: seconds, steps per synchronised run (see run_infer)
+DUMP_MAX_ELEMS = 14 << 20           # per array (58.7 MB in fp32; the B = 8 head map's written channels are 13.0 M): larger arrays are sampled
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: each (name, tensor) as out_dir/<name>.npy, float32 (float64 for integer data).  An array of more than DUMP_MAX_ELEMS elements
+    is written as `<name>_sample`: the elements at a fixed, seeded (seed 0), sorted set of DUMP_MAX_ELEMS flat positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays:
+        a = t.detach().cpu()
+        a = (a.float() if a.is_floating_point() else a.double()).numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a, name = a.reshape(-1)[pick], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def infer_outputs(out):
+    """What a caller of the forward+decode step receives: the (B,K,14) rows (zero in invalid slots: only valid rows are defined), the
+    (B,K,5) top-K table, the (B,K) validity flags and the written channels of the fp32 head map ([0:3] class logits, [8:58] regression)."""
+    import torch
+    det, topk, valid, hm = out
+    return [("rows", torch.where(valid.bool()[..., None], det, torch.zeros_like(det))), ("topk", topk), ("valid", valid),
+            ("head_map", torch.cat([hm[..., :3], hm[..., 8:58]], dim=-1))]
 
 
 def respawn_under_torchrun(args):
@@ -389,12 +429,24 @@ def run_infer(args, rank, world, device, dtype=None, leg=False):
                 print("hipGraph capture failed (%s); timing eager launches" % e, file=sys.stderr)
                 graph, mode = None, "eager"
         run = graph.replay if graph is not None else step
+        # warm-up on the timed path itself: at least --warmup steps and WARMUP_S seconds, in synchronised runs of WARMUP_RUN steps (the host
+        # must not queue seconds of work ahead), then one untimed region of --steps steps.  A plain run times ONE region, and the first region
+        # of a process came out 0.5-2 % slower than the ones after it (MI355X, B = 8 bf16: 2.525 vs 2.485 ms); after this warm-up it does not
+        n_warm, t_warm = 0, time.perf_counter() + WARMUP_S
+        while n_warm < args.warmup or time.perf_counter() < t_warm:
+            for _ in range(WARMUP_RUN):
+                run()
+            n_warm += WARMUP_RUN
+            torch.cuda.synchronize()
+        timed_repeats(run, args.steps, 1, 0, device)
 
         elapsed, n_img, all_s = timed_repeats(run, args.steps, 1 if leg else args.repeats, B * args.steps, device)
         det, topk, valid, hm = out
         if isinstance(hm, list):
             hm = torch.cat(hm)
             out = (det, topk, valid, hm)
+        if args.dump_outputs and not leg and rank == 0:
+            dump_outputs(args.dump_outputs, infer_outputs(out))
         if leg:
             feat = model.backbone.forward_nhwc(images)
             pk = model.heads.predictor._pack(ops.compute_tag(model.heads.predictor, feat.dtype))
@@ -422,19 +474,17 @@ def run_infer(args, rank, world, device, dtype=None, leg=False):
                     **({"operand_range_ok": bool(lib.f16x2_range_ok())} if dtype == "fp16x2" else {}),     # the split mode's one precondition: |activation| <= 65504
                     "vs_reference": deviation_vs_reference(out, dtype)}
 
-        # ---- roofline of the dominant kernel (fused heads: 46 % of the forward FLOPs), HIP events on the launch stream
-        feat = model.backbone.forward_nhwc(images)
-        pk = model.heads.predictor._pack(ops.compute_tag(model.heads.predictor, feat.dtype))
-        for _ in range(3):
-            ops.heads_fused(feat, pk)
-        heads_ms = _hip_event_ms(lambda: ops.heads_fused(feat, pk), 20)
+        if args.full:
+            # ---- roofline of the dominant kernel (fused heads: 46 % of the forward FLOPs), HIP events on the launch stream
+            feat = model.backbone.forward_nhwc(images)
+            pk = model.heads.predictor._pack(ops.compute_tag(model.heads.predictor, feat.dtype))
+            for _ in range(3):
+                ops.heads_fused(feat, pk)
+            heads_ms = _hip_event_ms(lambda: ops.heads_fused(feat, pk), 20)
 
-        fam = None if args.no_families else family_rooflines(model, images, tg, dtype, B, heads_ms)
+            fam = None if args.no_families else family_rooflines(model, images, tg, dtype, B, heads_ms)
     if rank != 0:
         return None
-    peak = PEAK_F32_TFLOPS if dtype == "fp32" else PEAK_BF16_TFLOPS          # (dense fp16 MFMA = the bf16 rate; fp16x2 issues 3 fp16 products per multiply)
-    achieved = HEADS_GFLOP_PER_IMG * B / heads_ms                # GFLOP / ms = TFLOP/s
-    traffic, traffic_source = heads_traffic(dtype, B)
     res = {
         "metric": "images/sec at 1280x384, DLA-34+DCNv2 forward+decode",
         "value": round(n_img / elapsed, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -451,15 +501,20 @@ def run_infer(args, rank, world, device, dtype=None, leg=False):
                    "h2d_excluded": True, "d2h_excluded": True,
                    "timed_region": "graph replays only: the fp32 image batch is already in HBM and the (B,50,14) rows stay "
                                    "on the device (the reference's timer includes the D2H, engine/inference.py:35-43)",
-                   **({"operand_range_ok": bool(lib.f16x2_range_ok())} if dtype == "fp16x2" else {}),
-                   "vs_reference": deviation_vs_reference(out, dtype)},
-        "roofline": {"kernel": "heads_fused_kernel", "bound": "mfma", "achieved": round(achieved, 2), "peak": peak,
-                     "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_source,
-                     "avg_launch_ms": round(heads_ms, 4),
-                     "algorithmic_flops_per_launch": HEADS_GFLOP_PER_IMG * B * 1e9,
-                     **({"mfma_products_per_multiply": 3, "frac_of_issued_mfma_work": round(3 * achieved / peak, 4)} if dtype == "fp16x2" else {})},
-        "roofline_families": fam,
+                   **({"operand_range_ok": bool(lib.f16x2_range_ok())} if dtype == "fp16x2" else {})},
     }
+    if not args.full:
+        return res
+    peak = PEAK_F32_TFLOPS if dtype == "fp32" else PEAK_BF16_TFLOPS          # (dense fp16 MFMA = the bf16 rate; fp16x2 issues 3 fp16 products per multiply)
+    achieved = HEADS_GFLOP_PER_IMG * B / heads_ms                # GFLOP / ms = TFLOP/s
+    traffic, traffic_source = heads_traffic(dtype, B)
+    res["config"]["vs_reference"] = deviation_vs_reference(out, dtype)
+    res["roofline"] = {"kernel": "heads_fused_kernel", "bound": "mfma", "achieved": round(achieved, 2), "peak": peak,
+                       "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_source,
+                       "avg_launch_ms": round(heads_ms, 4),
+                       "algorithmic_flops_per_launch": HEADS_GFLOP_PER_IMG * B * 1e9,
+                       **({"mfma_products_per_multiply": 3, "frac_of_issued_mfma_work": round(3 * achieved / peak, 4)} if dtype == "fp16x2" else {})}
+    res["roofline_families"] = fam
     if not args.no_cpu_baseline and world == 1:
         try:
             res["cpu_baseline"] = cpu_baseline(sd, args.cpu_baseline_images)
@@ -701,10 +756,15 @@ def run_train(args, rank, world, device, steps=None, warmup=None, leg=False, dty
         applied = min(int(st["step"]) for st in opt.state.values()) if opt.state else 0
         total = warmup + steps * len(all_s)                            # (GraphedTrainStep's capture warm-up is rolled back: it counts no steps)
         loss_scale_info = {"loss_scale": float(scaler.scale), "optimizer_steps_applied": applied, "optimizer_steps_run": total}
+    if args.dump_outputs and not leg and rank == 0:
+        # what the step hands back (the loss) and what it changed (the parameters, flattened in named_parameters order)
+        dump_outputs(args.dump_outputs, [("loss", last[0].reshape(1)),
+                                         ("parameters", torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]))])
 
-    # ---- roofline of the dominant training kernel family, timed live on one representative layer
-    from tools.train_layer_bench import dominant_kernel_roofline
-    roof = dominant_kernel_roofline(dtype, B, device)
+    if args.full:
+        # ---- roofline of the dominant training kernel family, timed live on one representative layer
+        from tools.train_layer_bench import dominant_kernel_roofline
+        roof = dominant_kernel_roofline(dtype, B, device)
     if rank != 0:
         return None
     res = {
@@ -721,8 +781,10 @@ def run_train(args, rank, world, device, steps=None, warmup=None, leg=False, dty
                               "ms_per_step_each": [round(1e3 * t / steps, 4) for t in all_s]},
                    "model_tflops_per_s": round(TRAIN_GFLOP_PER_IMG * n_img / elapsed / 1e3, 2), "loss_last_step": loss_v,
                    "h2d_excluded": True, "bn_one_launch_barriers_ok": bool(lib.bn_onepass_ok()), **loss_scale_info},
-        "roofline": roof,
     }
+    if not args.full:
+        return res
+    res["roofline"] = roof
     if leg:
         return res
     if not args.no_cpu_baseline and world == 1:
@@ -783,7 +845,7 @@ def main():
         res = run_train(args, rank, world, device)
     else:
         res = run_infer(args, rank, world, device)
-        if args.legs == "all" and args.dtype == "bf16" and not args.no_graph:
+        if args.full and args.legs == "all" and args.dtype == "bf16" and not args.no_graph:
             import gc
             import threading
             legs = {}
