@@ -51,6 +51,8 @@ const char* mfx_last_error(void);
  * Tuning/debug overrides: "conv_tile" | "dcn_tile" | "cat_tile" (tile id, 0 = automatic), "kc" (4 | 8 | 0),
  * "halo" (0 = generic kernel only, 1 = automatic, 2.. = force LDS-halo variant), "halo_cg", "dcn_wave", "dcn_patch" (same
  * convention), "ksplit" / "dcn_ksplit" (split-K factor), "topk_strips" (row strips of the top-K stage, 1 = single workgroup),
+ * "topk_merge_threads" (64..512, a multiple of 64) / "topk_merge_z" (1..64): the top-K merge's workgroup size and workgroups per map
+ * (other values return MFX_ERR_ARG and leave the switch unchanged),
  * "wgrad_*" / "dcn_wgrad_m" (training GEMM partitioning), "heads_persist" (1 = one workgroup per resident slot over (tile, branch)
  * unit ranges, n > 1 = n workgroups, 0 = one workgroup per tile), "heads_planes", "heads_dbg" (timing probes: wrong results).
  * Unknown names return MFX_ERR_ARG. */
@@ -62,7 +64,13 @@ int mfx_reset_options(void);
 int mfx_commit_options(void);
 /* Dispatch counters since process start, so a test can assert WHICH kernel variant a call took: "dcn_bt_fused" = launches of the
  * fused sample + weight-gradient kernel of mfx_dcn_backward_v2 (selected for bf16 / fp16, C = Cout = 64, W % 32 == 0 and at least
- * option "dcn_bt_fuse_min_chunks" (default 1024) 32-pixel chunks).  Unknown names return MFX_ERR_ARG (negative). */
+ * option "dcn_bt_fuse_min_chunks" (default 1024) 32-pixel chunks).
+ * Forward dispatch, one count per launch of the family that mfx_dcn_nhwc / mfx_conv2d_nhwc chose:
+ *   "dcn_lds" (16-bit LDS-patch kernel, dcn_lds.hip), "dcn_lds_of" (those of them that computed the offset conv inside),
+ *   "dcn_lds_split" (split-precision LDS kernel), "dcn_patch", "dcn_wave", "dcn_gather" (the implicit-GEMM gather kernel);
+ *   "conv_cw" / "conv_cws" (compile-time-geometry halo kernels, 16-bit / split precision), "conv_halo" (run-time-geometry halo kernel),
+ *   "conv_igemm" (generic implicit-GEMM kernel), "conv_splitk" (those of them that split K over workgroups).
+ * Unknown names return MFX_ERR_ARG (negative). */
 long mfx_get_counter(const char* name);
 
 /* Range sentinel of the split-precision mode (dtype MFX_F16X2: fp32 activations become fp16 (hi, lo) MFMA operand pairs; hi overflows above

@@ -22,6 +22,8 @@
 #include <cstdlib>
 #include <type_traits>
 
+extern long g_cnt_conv_cw, g_cnt_conv_cws, g_cnt_conv_halo;     // dispatch counters (conv_kernels.hip, mfx_get_counter)
+
 namespace mfx {
 
 struct HaloGeom {
@@ -571,6 +573,7 @@ static int try_conv_halo_impl(const mfx_conv_desc* d, hipStream_t st) {
         // compile-time-geometry form of the same decomposition (conv_cw.hip): bit-identical output
         const int r = try_conv_cw(d, v, st);
         if (r == 0 && d->stats) g_halo_stats_ran = true;
+        if (r == 0) ++g_cnt_conv_cw;
         if (r <= 0) return r == 0 ? 1 : r;
         static const bool trace = getenv("MFX_TRACE_CW") != nullptr;      // which layers stay on the run-time-geometry kernel
         if (trace) fprintf(stderr, "cw-fallback v=%d Ck=%d Cout=%d/%d s=%d HxW=%dx%d B=%d stats=%d out=%d res=%d act=%d\n", v, d->Ck, d->Cout, d->Cout_pad, d->stride,
@@ -579,6 +582,7 @@ static int try_conv_halo_impl(const mfx_conv_desc* d, hipStream_t st) {
     if (d->dtype == MFX_F16X2 && g_opt_halo_cg <= 0 && g_opt_halo_pair) {
         // split precision, compile-time-geometry form of the pair-walking kernel (conv_cws.hip): bit-identical output
         const int r = try_conv_cws(d, v, st);
+        if (r == 0) ++g_cnt_conv_cws;
         if (r <= 0) return r == 0 ? 1 : r;
     }
     int rc;
@@ -587,6 +591,7 @@ static int try_conv_halo_impl(const mfx_conv_desc* d, hipStream_t st) {
     else if (d->dtype == MFX_F16) rc = d->out_dtype == MFX_F16 ? halo_variant<half_t, half_t>(v, d, st) : halo_variant<half_t, float>(v, d, st);
     else if (d->out_dtype == MFX_BF16) rc = halo_variant<bf16_t, bf16_t>(v, d, st);
     else rc = halo_variant<bf16_t, float>(v, d, st);
+    if (rc == MFX_OK) ++g_cnt_conv_halo;
     return rc == MFX_OK ? 1 : rc;
 }
 

@@ -297,6 +297,9 @@ extern int g_opt_halo_cw, g_opt_cw_rows6, g_opt_halo_cws;
 extern int g_opt_halo, g_opt_halo_cg, g_opt_halo_pair, g_opt_halo_s2, g_opt_dcn_wave, g_opt_dcn_patch, g_opt_dcn_patch_fn8, g_opt_dcn_wgrad_m;
 }
 extern long g_cnt_dcn_bt_fused, g_cnt_dcn_bt_fly;
+// dispatch counters (mfx_get_counter): launches of each kernel family mfx_dcn_nhwc / mfx_conv2d_nhwc chose, since process start
+long g_cnt_dcn_lds = 0, g_cnt_dcn_lds_of = 0, g_cnt_dcn_lds_split = 0, g_cnt_dcn_patch = 0, g_cnt_dcn_wave = 0, g_cnt_dcn_gather = 0;
+long g_cnt_conv_cw = 0, g_cnt_conv_cws = 0, g_cnt_conv_halo = 0, g_cnt_conv_igemm = 0, g_cnt_conv_splitk = 0;
 extern int g_opt_ext_bwd_fast;
 extern int g_opt_dcn_bt_fly;
 extern int g_opt_wgrad_min_m;
@@ -345,7 +348,9 @@ static int launch_conv(const mfx_conv_desc* d, const ConvGeom& g, EpiArgs ep, hi
             if ((size_t)ksplit * d->M * d->Cout_pad * sizeof(float) > (size_t)d->workspace_bytes) ksplit = 1;
         }
     }
+    ++g_cnt_conv_igemm;
     if (ksplit > 1) {
+        ++g_cnt_conv_splitk;
         ep.ksplit = ksplit; ep.ws = reinterpret_cast<float*>(d->workspace); ep.ws_ld = d->Cout_pad;
         hipLaunchKernelGGL(k, dim3(tiles, ksplit), dim3(WM * WN * 64), smem, st, reinterpret_cast<const T*>(d->x),
                            reinterpret_cast<const T*>(d->w), g, d->rowmap, ep);
@@ -460,6 +465,9 @@ extern "C" int mfx_set_option(const char* name, int value) {
 #endif
     int* slot = option_slot(n);
     if (!slot) return mfx_fail(MFX_ERR_ARG, "set_option: unknown option");
+    if (n == "topk_merge_threads" && (value < 64 || value > 512 || value % 64 != 0))      // the merge ranks by whole wavefronts; 512 = its __launch_bounds__
+        return mfx_fail(MFX_ERR_ARG, "set_option: topk_merge_threads must be a multiple of 64 in 64..512");
+    if (n == "topk_merge_z" && (value < 1 || value > 64)) return mfx_fail(MFX_ERR_ARG, "set_option: topk_merge_z must be in 1..64");
     auto& defs = option_defaults();
     bool seen = false;
     for (const auto& e : defs) seen = seen || e.first == slot;
@@ -493,6 +501,12 @@ extern "C" long mfx_get_counter(const char* name) {
     const std::string n(name);
     if (n == "dcn_bt_fused") return g_cnt_dcn_bt_fused;
     if (n == "dcn_bt_fly") return g_cnt_dcn_bt_fly;
+    static const std::pair<const char*, const long*> dispatch[] = {
+        {"dcn_lds", &g_cnt_dcn_lds}, {"dcn_lds_of", &g_cnt_dcn_lds_of}, {"dcn_lds_split", &g_cnt_dcn_lds_split}, {"dcn_patch", &g_cnt_dcn_patch},
+        {"dcn_wave", &g_cnt_dcn_wave}, {"dcn_gather", &g_cnt_dcn_gather}, {"conv_cw", &g_cnt_conv_cw}, {"conv_cws", &g_cnt_conv_cws},
+        {"conv_halo", &g_cnt_conv_halo}, {"conv_igemm", &g_cnt_conv_igemm}, {"conv_splitk", &g_cnt_conv_splitk}};
+    for (const auto& e : dispatch)
+        if (n == e.first) return *e.second;
     return mfx_fail(MFX_ERR_ARG, "get_counter: unknown counter");
 }
 
@@ -621,6 +635,7 @@ static int launch_dcn(const mfx_dcn_desc* d, const DcnGeom& g, EpiArgs ep, hipSt
         while (ksplit > 1 && ((ep.nk + ksplit - 1) / ksplit) * (ksplit - 1) >= ep.nk) --ksplit;
         if ((size_t)ksplit * g.M * d->Cout_pad * sizeof(float) > (size_t)d->workspace_bytes) ksplit = 1;
     }
+    ++g_cnt_dcn_gather;
     if (ksplit > 1) {
         ep.ksplit = ksplit; ep.ws = reinterpret_cast<float*>(d->workspace); ep.ws_ld = d->Cout_pad;
         hipLaunchKernelGGL(k, dim3(tiles, ksplit), dim3(WM * WN * 64), smem, st, reinterpret_cast<const T*>(d->x), d->offmask,
@@ -675,11 +690,18 @@ extern "C" int mfx_dcn_nhwc(const mfx_dcn_desc* d, void* stream) {
     if ((size_t)d->B * d->H * d->W * d->C * (elems == 8 ? 2 : 4) >= ((size_t)1 << 32))
         return mfx_fail(MFX_ERR_UNSUPPORTED, "dcn: input tensor of 4 GB or more (the gather kernels address it with 32-bit byte offsets)");
     if (!d->nonsquare) {                                      // (the LDS-patch / wave kernels are built for square geometry)
+        const bool of = dcn_lds_fuses_offset_conv(d);         // (decided before the launch: the same test try_dcn_lds makes)
         int h = try_dcn_lds(d, reinterpret_cast<hipStream_t>(stream));
+        if (h > 0) {
+            if (d->dtype == MFX_F16X2) ++g_cnt_dcn_lds_split;
+            else { ++g_cnt_dcn_lds; if (of) ++g_cnt_dcn_lds_of; }
+        }
         if (h != 0) return h < 0 ? h : MFX_OK;
         h = try_dcn_patch(d, reinterpret_cast<hipStream_t>(stream));
+        if (h > 0) ++g_cnt_dcn_patch;
         if (h != 0) return h < 0 ? h : MFX_OK;
         h = try_dcn_wave(d, reinterpret_cast<hipStream_t>(stream));
+        if (h > 0) ++g_cnt_dcn_wave;
         if (h != 0) return h < 0 ? h : MFX_OK;
     }
     EpiArgs ep;

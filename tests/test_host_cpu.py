@@ -182,6 +182,18 @@ def test_c_abi_argument_errors_need_no_gpu():
     lib = L.load()
     null = ctypes.c_void_p(None)
     assert lib.mfx_set_option(b"no_such_option", 1) != 0 and b"unknown option" in lib.mfx_last_error()
+    # the top-K merge's launch shape: whole wavefronts up to its 512-thread launch bound, 1..64 workgroups per map (nothing launches here)
+    try:
+        for bad in (0, -64, 32, 96, 100, 576, 1024):
+            assert lib.mfx_set_option(b"topk_merge_threads", bad) != 0 and b"topk_merge_threads" in lib.mfx_last_error(), bad
+        for bad in (0, -1, 65, 1000):
+            assert lib.mfx_set_option(b"topk_merge_z", bad) != 0 and b"topk_merge_z" in lib.mfx_last_error(), bad
+        for ok in (64, 128, 192, 448, 512):
+            assert lib.mfx_set_option(b"topk_merge_threads", ok) == 0, ok
+        for ok in (1, 2, 16, 64):
+            assert lib.mfx_set_option(b"topk_merge_z", ok) == 0, ok
+    finally:
+        lib.mfx_reset_options()
     assert lib.mfx_kitti_encode_targets(None, null) != 0 and b"null descriptor" in lib.mfx_last_error()
     d = L.KittiDesc()
     d.B, d.max_objs, d.in_w, d.in_h, d.down, d.num_classes = 1, 40, 1281, 384, 4, 3         # width not divisible by the stride
