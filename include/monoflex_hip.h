@@ -70,6 +70,13 @@ int mfx_commit_options(void);
  *   "dcn_lds_split" (split-precision LDS kernel), "dcn_patch", "dcn_wave", "dcn_gather" (the implicit-GEMM gather kernel);
  *   "conv_cw" / "conv_cws" (compile-time-geometry halo kernels, 16-bit / split precision), "conv_halo" (run-time-geometry halo kernel),
  *   "conv_igemm" (generic implicit-GEMM kernel), "conv_splitk" (those of them that split K over workgroups).
+ * Training dispatch, host-side launch counts (no device work):
+ *   weight gradients: "wgrad_patch" / "wgrad_tr" (the workspace kernels of wgrad_tr.hip), "wgrad_mfma" (the MFMA slab kernel, with or without
+ *   workspace), "wgrad_valu" (the VALU kernel), "wgrad_reduce" (every slab reduction, DCN weight gradients included), "stem_wgrad";
+ *   BN: "bn_fwd_onepass" / "bn_bwd_onepass" (one-launch grid-barrier kernels), "bn_fwd_two" / "bn_bwd_two" (mfx_bn_train_fwd / _bwd calls
+ *   that took the two-launch form), "conv_bn_stats" (convs whose epilogue accumulated the following BN's statistics);
+ *   DCN backward: "dcn_bt_tile" (dcn_bwd_tile_kernel), "dcn_bt_sample" (dcn_bwd_sample_kernel), "dcn_bt_far" (far-corner kernels, both forms);
+ *   "gram" (mfx_gram_heads phase calls), "adamw_multi" (one-launch AdamW).
  * Unknown names return MFX_ERR_ARG (negative). */
 long mfx_get_counter(const char* name);
 

@@ -11,6 +11,8 @@
 #include "err.h"
 #include "common.h"
 
+extern long g_cnt_adamw_multi;      // dispatch counter (conv_kernels.hip, mfx_get_counter)
+
 namespace mfx {
 
 constexpr int AW_CHUNK = 4096;
@@ -87,6 +89,7 @@ extern "C" int mfx_adamw_multi(const mfx_adamw_desc* descs_dev, const long long*
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(adamw_bump_steps_kernel, dim3(1), dim3(256), 0, st, descs_dev, n, found_inf);
     hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, st, descs_dev, prefix_dev, n, groups_dev, found_inf);
+    ++g_cnt_adamw_multi;
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }

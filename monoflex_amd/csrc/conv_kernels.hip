@@ -300,6 +300,11 @@ extern long g_cnt_dcn_bt_fused, g_cnt_dcn_bt_fly;
 // dispatch counters (mfx_get_counter): launches of each kernel family mfx_dcn_nhwc / mfx_conv2d_nhwc chose, since process start
 long g_cnt_dcn_lds = 0, g_cnt_dcn_lds_of = 0, g_cnt_dcn_lds_split = 0, g_cnt_dcn_patch = 0, g_cnt_dcn_wave = 0, g_cnt_dcn_gather = 0;
 long g_cnt_conv_cw = 0, g_cnt_conv_cws = 0, g_cnt_conv_halo = 0, g_cnt_conv_igemm = 0, g_cnt_conv_splitk = 0;
+// training-side families (incremented in train_kernels.hip, wgrad_tr.hip, gram_heads.hip, adamw.hip; conv_bn_stats here)
+long g_cnt_wgrad_patch = 0, g_cnt_wgrad_tr = 0, g_cnt_wgrad_mfma = 0, g_cnt_wgrad_valu = 0, g_cnt_wgrad_reduce = 0, g_cnt_stem_wgrad = 0;
+long g_cnt_bn_fwd_onepass = 0, g_cnt_bn_bwd_onepass = 0, g_cnt_bn_fwd_two = 0, g_cnt_bn_bwd_two = 0, g_cnt_conv_bn_stats = 0;
+long g_cnt_gram = 0, g_cnt_adamw_multi = 0;
+extern long g_cnt_dcn_bt_tile, g_cnt_dcn_bt_sample, g_cnt_dcn_bt_far;
 extern int g_opt_ext_bwd_fast;
 extern int g_opt_dcn_bt_fly;
 extern int g_opt_wgrad_min_m;
@@ -504,7 +509,12 @@ extern "C" long mfx_get_counter(const char* name) {
     static const std::pair<const char*, const long*> dispatch[] = {
         {"dcn_lds", &g_cnt_dcn_lds}, {"dcn_lds_of", &g_cnt_dcn_lds_of}, {"dcn_lds_split", &g_cnt_dcn_lds_split}, {"dcn_patch", &g_cnt_dcn_patch},
         {"dcn_wave", &g_cnt_dcn_wave}, {"dcn_gather", &g_cnt_dcn_gather}, {"conv_cw", &g_cnt_conv_cw}, {"conv_cws", &g_cnt_conv_cws},
-        {"conv_halo", &g_cnt_conv_halo}, {"conv_igemm", &g_cnt_conv_igemm}, {"conv_splitk", &g_cnt_conv_splitk}};
+        {"conv_halo", &g_cnt_conv_halo}, {"conv_igemm", &g_cnt_conv_igemm}, {"conv_splitk", &g_cnt_conv_splitk},
+        {"wgrad_patch", &g_cnt_wgrad_patch}, {"wgrad_tr", &g_cnt_wgrad_tr}, {"wgrad_mfma", &g_cnt_wgrad_mfma}, {"wgrad_valu", &g_cnt_wgrad_valu},
+        {"wgrad_reduce", &g_cnt_wgrad_reduce}, {"stem_wgrad", &g_cnt_stem_wgrad}, {"bn_fwd_onepass", &g_cnt_bn_fwd_onepass},
+        {"bn_bwd_onepass", &g_cnt_bn_bwd_onepass}, {"bn_fwd_two", &g_cnt_bn_fwd_two}, {"bn_bwd_two", &g_cnt_bn_bwd_two},
+        {"conv_bn_stats", &g_cnt_conv_bn_stats}, {"dcn_bt_tile", &g_cnt_dcn_bt_tile}, {"dcn_bt_sample", &g_cnt_dcn_bt_sample},
+        {"dcn_bt_far", &g_cnt_dcn_bt_far}, {"gram", &g_cnt_gram}, {"adamw_multi", &g_cnt_adamw_multi}};
     for (const auto& e : dispatch)
         if (n == e.first) return *e.second;
     return mfx_fail(MFX_ERR_ARG, "get_counter: unknown counter");
@@ -537,7 +547,7 @@ extern "C" int mfx_conv2d_nhwc(const mfx_conv_desc* d, void* stream) {
         int ran = 0;
         const int h = try_conv_halo(d, reinterpret_cast<hipStream_t>(stream), &ran);   // 3x3/s1: LDS-staged halo kernel
         if (h != 0) {
-            if (h > 0 && ran && d->stats_done) *d->stats_done = 1;
+            if (h > 0 && ran && d->stats_done) { *d->stats_done = 1; ++g_cnt_conv_bn_stats; }
             return h < 0 ? h : MFX_OK;
         }
     }

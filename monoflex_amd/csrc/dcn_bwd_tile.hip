@@ -44,6 +44,8 @@ long g_cnt_dcn_bt_fly = 0;         // counter "dcn_bt_fly": backward calls that 
 int g_opt_dcn_bt_fuse_wgrad = 1;   // option "dcn_bt_fuse_wgrad": 64 -> 64 bf16 layers accumulate grad_weight inside the sample kernel (no columns in memory)
 int g_opt_dcn_bt_fuse_min_chunks = 1024; // option "dcn_bt_fuse_min_chunks": fewer 32-pixel chunks than this keep the unfused kernels (tests lower it)
 long g_cnt_dcn_bt_fused = 0;   // counter "dcn_bt_fused": launches of dcn_bwd_sample_wgrad_kernel since process start
+long g_cnt_dcn_bt_tile = 0, g_cnt_dcn_bt_sample = 0, g_cnt_dcn_bt_far = 0;   // counters "dcn_bt_tile" / "dcn_bt_sample" / "dcn_bt_far": launches of
+                               // dcn_bwd_tile_kernel, of dcn_bwd_sample_kernel, of dcn_bwd_far_kernel + dcn_bwd_far_fly_kernel
 int g_opt_dcn_bt_cs = 0;       // option "dcn_bt_cs": channel slice of the tile kernel for C >= 128 (0 = by workgroup count, 64, 128)
 int g_opt_dcn_bt_cs_wgs = 1000; // option "dcn_bt_cs_wgs": below this many 128-channel workgroups the tile kernel takes 64-channel slices
 int g_opt_dcn_bt_dbg = 0;      // option "dcn_bt_dbg": experiment switches of dcn_bwd_tile_kernel (0 in production)
@@ -1310,10 +1312,12 @@ static int dcn_backward_v2_impl(const T* x, const float* offmask, const float* w
                 const size_t smem = (size_t)BT_NPIX * BtEntry<T>::LCAP * sizeof(typename BtEntry<T>::type) + (size_t)BT_NPIX * 4 + (size_t)BT_FCAP * 8;
                 hipLaunchKernelGGL((dcn_bwd_tile_kernel<T, 8>), grid, dim3(256), smem, st, offmask, (const T*)gcol, g, dx, cnt, flist, far_cap);
                 hipLaunchKernelGGL(dcn_bwd_far_kernel<T>, dim3(1024), dim3(256), 0, st, (const T*)gcol, (const u32x4*)flist, (const int*)cnt, far_cap, g, dx);
+                ++g_cnt_dcn_bt_tile; ++g_cnt_dcn_bt_far;
             } else {
             const size_t smem = (size_t)BT_NPIX * FZ_LCAP * 4 + (size_t)BT_NPIX * 4 + (size_t)BT_FCAP * 8;      // 36 KB: four workgroups per CU (the epilogue's 4 x 8.7 KB stages overlay it)
             hipLaunchKernelGGL(dcn_bwd_tile_fly_kernel<T>, dim3((unsigned)(g.tiles_x * g.tiles_y * B)), dim3(256), smem, st, offmask, dy, (const T*)wT, g, dx, cnt, flist, far_cap);
             hipLaunchKernelGGL(dcn_bwd_far_fly_kernel<T>, dim3(1024), dim3(256), 0, st, dy, (const T*)wT, (const u32x4*)flist, (const int*)cnt, far_cap, g, dx);
+            ++g_cnt_dcn_bt_far;
             }
             MFX_HIP_CHECK(hipGetLastError());
             return bias_in_kernel ? MFX_OK : mfx_internal_colsum_add(dy, dbias, M, Cout, Cout, dt, stream);
@@ -1365,6 +1369,7 @@ static int dcn_backward_v2_impl(const T* x, const float* offmask, const float* w
         const dim3 sgrid((unsigned)rows, (unsigned)xsplit);
         if (gs.CS == 64) hipLaunchKernelGGL((dcn_bwd_sample_kernel<T, 8>), sgrid, dim3(256), 0, st, x, offmask, (const T*)gcol, gs, xsplit, d_raw, col);
         else hipLaunchKernelGGL((dcn_bwd_sample_kernel<T, 16>), sgrid, dim3(256), 0, st, x, offmask, (const T*)gcol, gs, xsplit, d_raw, col);
+        ++g_cnt_dcn_bt_sample;
     }
     if (g_opt_det) {
         // grad_input through the fixed-point map (the far-corner list's memory: 9 * M * C bytes >= 8 * M * C); see dcn_bwd_dx_fixed_kernel
@@ -1380,6 +1385,7 @@ static int dcn_backward_v2_impl(const T* x, const float* offmask, const float* w
     if (g.CS == 64) hipLaunchKernelGGL((dcn_bwd_tile_kernel<T, 8>), grid, dim3(256), smem, st, offmask, (const T*)gcol, g, dx, cnt, flist, far_cap);
     else hipLaunchKernelGGL((dcn_bwd_tile_kernel<T, 16>), grid, dim3(256), smem, st, offmask, (const T*)gcol, g, dx, cnt, flist, far_cap);
     hipLaunchKernelGGL(dcn_bwd_far_kernel<T>, dim3(1024), dim3(256), 0, st, (const T*)gcol, (const u32x4*)flist, (const int*)cnt, far_cap, g, dx);
+    ++g_cnt_dcn_bt_tile; ++g_cnt_dcn_bt_far;
     MFX_HIP_CHECK(hipGetLastError());
     }
     // grad_weight[o][c][tap] = sum_m dy[m][o] * col[m][tap*C + c]: MFMA GEMM over the pixels, written as (Cout, C, 3, 3)

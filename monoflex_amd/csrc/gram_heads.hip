@@ -25,6 +25,8 @@
 #include "fill.h"
 #include <algorithm>
 
+extern long g_cnt_gram;      // dispatch counter (conv_kernels.hip, mfx_get_counter)
+
 namespace mfx {
 
 constexpr int GK = 576, GC = 64, GT = 256;     // patch length (9 taps x 64 channels), input channels, trunk channels per branch
@@ -585,6 +587,7 @@ extern "C" int mfx_gram_heads(const mfx_gram_desc* d, int phase, void* stream) {
     for (int b = 0; b < d->nbranch; ++b)
         if (d->k[b] < 1 || d->k[b] > 32 || d->off[b] < 0 || d->off[b] + d->k[b] > d->ld_out) return mfx_fail(MFX_ERR_ARG, "gram_heads: branch outputs out of range");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (d->dtype == MFX_BF16 || d->dtype == MFX_F16) ++g_cnt_gram;       // one count per phase call
     if (d->dtype == MFX_BF16) return gram_phase<bf16_t>(d, phase, st);
     if (d->dtype == MFX_F16) return gram_phase<half_t>(d, phase, st);
     return mfx_fail(MFX_ERR_UNSUPPORTED, "gram_heads: 16-bit activations only (fp32 runs the torch form, monoflex_amd/gram_heads.py)");

@@ -9,6 +9,10 @@
 #include "wgrad.h"
 #include <algorithm>
 
+// dispatch counters (conv_kernels.hip, mfx_get_counter): host-side launch counts of each weight-gradient / BN family
+extern long g_cnt_wgrad_patch, g_cnt_wgrad_tr, g_cnt_wgrad_mfma, g_cnt_wgrad_valu, g_cnt_wgrad_reduce;
+extern long g_cnt_bn_fwd_onepass, g_cnt_bn_bwd_onepass, g_cnt_bn_fwd_two, g_cnt_bn_bwd_two;
+
 namespace mfx {
 
 static inline int cdivt(long a, long b) { return (int)((a + b - 1) / b); }
@@ -1072,10 +1076,12 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw, int B, int 
     if (is16 && g_opt_wgrad_mfma) {
         int nslab_tr = 0;
         int rc_tr = try_conv_wgrad_patch(x, dy, g, dtype, workspace, workspace_bytes, &nslab_tr, st);
-        if (rc_tr != 1) rc_tr = try_conv_wgrad_tr(x, dy, g, dtype, workspace, workspace_bytes, &nslab_tr, st);
+        if (rc_tr == 1) ++g_cnt_wgrad_patch;
+        else if ((rc_tr = try_conv_wgrad_tr(x, dy, g, dtype, workspace, workspace_bytes, &nslab_tr, st)) == 1) ++g_cnt_wgrad_tr;
         if (rc_tr == 1) {
             const long total = (long)Cout * g.K;
             hipLaunchKernelGGL(wgrad_reduce_kernel, WR_GRID(total), dim3(256), 0, st, g.ws, nslab_tr, g.ws_slab, g.ws_ld, g, dw);
+            ++g_cnt_wgrad_reduce;
             MFX_HIP_CHECK(hipGetLastError());
             return MFX_OK;
         }
@@ -1101,6 +1107,7 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw, int B, int 
         if (ws_ok) { g.ws = reinterpret_cast<float*>(workspace); g.ws_ld = ws_ld; g.ws_slab = ws_slab; }
         else MFX_HIP_CHECK(mfx::zero_async(dw, dw_bytes, st));
         dim3 grid(cdivt(g.K, bt), cdivt(Cout, bt), cdivt(g.M, g.m_per_block));
+        ++g_cnt_wgrad_mfma;
         if (dtype == MFX_BF16) {
             if (bt == 128) hipLaunchKernelGGL((conv_wgrad_mfma_kernel<bf16_t, 128>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, g, dw);
             else hipLaunchKernelGGL((conv_wgrad_mfma_kernel<bf16_t, 64>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)dy, g, dw);
@@ -1111,6 +1118,7 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw, int B, int 
         if (ws_ok) {
             const long total = (long)Cout * g.K;
             hipLaunchKernelGGL(wgrad_reduce_kernel, WR_GRID(total), dim3(256), 0, st, g.ws, nslab, ws_slab, ws_ld, g, dw);
+            ++g_cnt_wgrad_reduce;
         }
         MFX_HIP_CHECK(hipGetLastError());
         return MFX_OK;
@@ -1118,6 +1126,7 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw, int B, int 
     MFX_HIP_CHECK(mfx::zero_async(dw, dw_bytes, st));
     if (g_opt_det) g.m_per_block = g.M;                          // one slab: every element of dw receives exactly one add
     dim3 grid(cdivt(g.K, 64), cdivt(Cout, 64), cdivt(g.M, g.m_per_block));
+    ++g_cnt_wgrad_valu;
     DISPATCH_T(dtype, hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (const float*)dy, g, dw),
                       hipLaunchKernelGGL(conv_wgrad_kernel<T16>, grid, dim3(256), 0, st, (const T16*)x, (const T16*)dy, g, dw));
     MFX_HIP_CHECK(hipGetLastError());
@@ -1130,6 +1139,7 @@ int mfx_internal_wgrad_slab_sum(const float* ws, int nslab, int Cout, int Ck, in
     g.Cout = Cout; g.Ck = Ck; g.kh = kh; g.kw = kw; g.K = kh * kw * Ck; g.oihw = 1; g.Cin_out = Ck; g.Cout_out = Cout;
     const long total = (long)Cout * g.K;
     hipLaunchKernelGGL(wgrad_reduce_kernel, WR_GRID(total), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), ws, nslab, total, g.K, g, dw_oihw);
+    ++g_cnt_wgrad_reduce;
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }
@@ -1707,8 +1717,9 @@ extern "C" int mfx_bn_train_fwd(const void* x, const void* res, void* y, const f
         int r = 1;
         DISPATCH_T(dtype, r = bn_fwd_onepass<float>(x, res, y, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, M, C, act, scratch, mean, rstd, st),
                           r = bn_fwd_onepass<T16>(x, res, y, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, M, C, act, scratch, mean, rstd, st));
-        if (r == 0) { MFX_HIP_CHECK(hipGetLastError()); return MFX_OK; }
+        if (r == 0) { ++g_cnt_bn_fwd_onepass; MFX_HIP_CHECK(hipGetLastError()); return MFX_OK; }
     }
+    ++g_cnt_bn_fwd_two;                                                 // (with stats_done the conv's epilogue took the statistics launch's place)
     if (!stats_done)
         DISPATCH_T(dtype, hipLaunchKernelGGL(bn_stats_kernel<float>, dim3(cdivt(M, rows)), dim3(256), smem, st, (const float*)x, M, C, rows, scratch, scratch + C, ncopy),
                           hipLaunchKernelGGL(bn_stats_kernel<T16>, dim3(cdivt(M, rows)), dim3(256), smem, st, (const T16*)x, M, C, rows, scratch, scratch + C, ncopy));
@@ -1782,8 +1793,9 @@ extern "C" int mfx_bn_train_bwd(const void* x, const void* a, const void* da, co
         int r = 1;
         DISPATCH_T(dtype, r = bn_bwd_onepass<float>(x, a, da, mean, rstd, gamma, beta, dx, dres, dgamma, dbeta, M, C, act, scratch, st),
                           r = bn_bwd_onepass<T16>(x, a, da, mean, rstd, gamma, beta, dx, dres, dgamma, dbeta, M, C, act, scratch, st));
-        if (r == 0) { MFX_HIP_CHECK(hipGetLastError()); return MFX_OK; }
+        if (r == 0) { ++g_cnt_bn_bwd_onepass; MFX_HIP_CHECK(hipGetLastError()); return MFX_OK; }
     }
+    ++g_cnt_bn_bwd_two;
     float* sums = scratch + BN_SCRATCH_COLS;
     DISPATCH_T(dtype,
         hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(cdivt(M, rows)), dim3(256), smem, st, (const float*)x, (const float*)a, (const float*)da, mean, rstd, M, C, rows, act, sums, sums + C, ncopy, gamma, beta),

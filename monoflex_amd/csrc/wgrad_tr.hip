@@ -22,6 +22,8 @@
 #include "wgrad.h"
 #include <algorithm>
 
+extern long g_cnt_stem_wgrad;      // dispatch counter (conv_kernels.hip, mfx_get_counter)
+
 namespace mfx {
 
 constexpr int TR_BK = 192, TR_STEP = 32;
@@ -681,6 +683,7 @@ extern "C" int mfx_stem_wgrad_16(const void* xp, const void* dy, float* dw, int 
     g.tiles_per_block = (g.ntiles + nb - 1) / nb;
     nb = (g.ntiles + g.tiles_per_block - 1) / g.tiles_per_block;
     g.ws = reinterpret_cast<float*>(workspace);
+    ++g_cnt_stem_wgrad;
     if (dtype == MFX_BF16) hipLaunchKernelGGL(stem_wgrad_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t*)xp, (const bf16_t*)dy, g);
     else hipLaunchKernelGGL(stem_wgrad_kernel<half_t>, dim3(nb), dim3(256), 0, st, (const half_t*)xp, (const half_t*)dy, g);
     hipLaunchKernelGGL(slab_sum_kernel, dim3((16 * SW_K + 63) / 64), dim3(256), 0, st, (const float*)g.ws, nb, 16 * SW_K, dw);

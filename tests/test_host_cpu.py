@@ -175,6 +175,21 @@ def test_ctypes_layouts_equal_the_c_compilers(tmp_path):
     assert seen == sum(len(ct._fields_) + 1 for ct in pairs.values())
 
 
+TRAIN_COUNTERS = ("wgrad_patch", "wgrad_tr", "wgrad_mfma", "wgrad_valu", "wgrad_reduce", "stem_wgrad", "bn_fwd_onepass", "bn_bwd_onepass",
+                  "bn_fwd_two", "bn_bwd_two", "conv_bn_stats", "dcn_bt_tile", "dcn_bt_sample", "dcn_bt_far", "gram", "adamw_multi")
+
+
+def test_dispatch_counter_names_need_no_gpu():
+    """mfx_get_counter: every documented family name is accepted (a count >= 0; no launch has happened in a CPU process, so 0), an unknown
+    name is still rejected with MFX_ERR_ARG."""
+    from monoflex_amd import lib as L
+    lib = L.load()
+    for n in TRAIN_COUNTERS + ("dcn_bt_fused", "dcn_bt_fly", "dcn_lds", "conv_igemm"):
+        assert lib.mfx_get_counter(n.encode()) == 0, n
+    for bad in (b"no_such_counter", b"", b"wgrad", b"bn_onepass", b"WGRAD_MFMA", b"gram "):
+        assert lib.mfx_get_counter(bad) < 0 and b"unknown counter" in lib.mfx_last_error(), bad
+
+
 def test_c_abi_argument_errors_need_no_gpu():
     """Error behaviour of the C boundary: bad arguments are rejected before any device work, with a code and a message
     (the reference raises through AT_ASSERTM / python asserts, SURVEY 8b 'Errors')."""
