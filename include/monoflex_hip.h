@@ -11,8 +11,12 @@
  *      (/root/reference/model/backbone/DCNv2/src/vision.cpp:3-8):
  *        dcn_v2_forward   src/dcn_v2.h:9-46   -> mfx_dcn_v2_forward
  *        dcn_v2_backward  src/dcn_v2.h:48-92  -> mfx_dcn_v2_backward
+ *        dcn_v2_psroi_pooling_forward   src/dcn_v2.h:94-138   -> mfx_dcn_v2_psroi_pooling_forward
+ *        dcn_v2_psroi_pooling_backward  src/dcn_v2.h:140-190  -> mfx_dcn_v2_psroi_pooling_backward
  *      Same layouts as the reference (NCHW fp32; offset channel 2k = dh, 2k+1 = dw of tap k;
- *      mask channel k), same argument meaning; outputs are caller-allocated instead of ATen-allocated.
+ *      mask channel k; ROI rows (batch_index, x1, y1, x2, y2); pooling offsets (N, 2*classes, part, part) with
+ *      channel 2c = x, 2c+1 = y of class c), same argument meaning; outputs are caller-allocated instead of
+ *      ATen-allocated.
  *  (2) The NHWC operators the rest of the path is built from (they replace what the reference gets
  *      from cuDNN/cuBLAS/torch through nn.Conv2d, BatchNorm2d, MaxPool2d, ConvTranspose2d, topk, ...;
  *      call sites cited per function).
@@ -116,6 +120,31 @@ int mfx_dcn_v2_backward(const float* input, const float* weight, const float* bi
                         int B, int C, int H, int W, int Cout, int kh, int kw,
                         int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
                         int deformable_group, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Deformable position-sensitive ROI pooling -- src/dcn_v2.h:94-138, kernel src/cuda/dcn_v2_psroi_pooling_cuda.cu:59-146, host checks :271-341.
+ * input (B,C,H,W), bbox (N,5) rows (batch_index, x1, y1, x2, y2), trans (trans_rois >= N, trans_channels = 2*num_classes, part_size, part_size)
+ * (ignored, may be NULL, when no_trans) -> output and output_count, both (N, output_dim, pooled_size, pooled_size); output_count is the number
+ * of samples a bin kept, as fp32.  Argument order: the reference's, with the tensor sizes in the middle.  Nothing is allocated and nothing
+ * synchronises; N == 0 returns MFX_OK without a launch.  Narrowed against the reference in two places:
+ *  - a ROI whose batch_index is outside [0, B) gives output 0 and count 0 (the reference reads out of bounds; the check is a guard on the device);
+ *  - C == output_dim is required as in the reference (:295, MFX_ERR_ARG), and with it group_size must be 1 (MFX_ERR_UNSUPPORTED): for any other
+ *    value the reference's channel index (ctop * group_size + gh) * group_size + gw runs past the input.
+ * Also MFX_ERR_UNSUPPORTED: sample_per_part > 32 (a bin's samples are held on chip). */
+int mfx_dcn_v2_psroi_pooling_forward(const float* input, const float* bbox, const float* trans, float* output, float* output_count,
+                                     int B, int C, int H, int W, int N, int trans_rois, int trans_channels,
+                                     int no_trans, float spatial_scale, int output_dim, int group_size, int pooled_size, int part_size,
+                                     int sample_per_part, float trans_std, void* stream);
+
+/* Its backward -- src/dcn_v2.h:140-190, kernel :149-269, host checks :343-418: grad_input (B,C,H,W) and grad_trans (the shape of trans; not
+ * touched when no_trans) are zero-filled on `stream` and then accumulated; top_count is the forward's output_count (bins with count <= 0 are
+ * skipped).  The formulas are the reference's: where a sample was clamped to the map the offset gradient ignores the clamp (:255-262).
+ * grad_trans is summed on chip in a fixed order and written by one thread per cell (run-to-run bitwise repeatable); grad_input is a scatter of
+ * fp32 atomic adds and depends on their order in its last bits.  Same narrowings as the forward; a ROI of no image contributes nothing. */
+int mfx_dcn_v2_psroi_pooling_backward(const float* out_grad, const float* input, const float* bbox, const float* trans, const float* top_count,
+                                      float* grad_input, float* grad_trans,
+                                      int B, int C, int H, int W, int N, int trans_rois, int trans_channels,
+                                      int no_trans, float spatial_scale, int output_dim, int group_size, int pooled_size, int part_size,
+                                      int sample_per_part, float trans_std, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (2) NHWC operators

@@ -132,6 +132,8 @@ SYMBOLS = {
     "mfx_dcn_v2_workspace_bytes_g": (_S, [_I] * 15),
     "mfx_dcn_v2_forward": (_I, [_P] * 6 + [_I] * 14 + [_P, _S, _P]),
     "mfx_dcn_v2_backward": (_I, [_P] * 11 + [_I] * 14 + [_P, _S, _P]),
+    "mfx_dcn_v2_psroi_pooling_forward": (_I, [_P] * 5 + [_I] * 8 + [_F] + [_I] * 5 + [_F, _P]),
+    "mfx_dcn_v2_psroi_pooling_backward": (_I, [_P] * 7 + [_I] * 8 + [_F] + [_I] * 5 + [_F, _P]),
     "mfx_conv2d_nhwc": (_I, [ctypes.POINTER(ConvDesc), _P]),
     "mfx_cat_conv1x1_nhwc": (_I, [ctypes.POINTER(CatDesc), _P]),
     "mfx_dcn_nhwc": (_I, [ctypes.POINTER(DcnDesc), _P]),

@@ -3,6 +3,9 @@ same four names, same positional arguments, served by libmonoflex_hip.so on gfx9
 
     dcn_v2_forward(input, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, dg) -> output
     dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, ...) -> [gi, goff, gmask, gw, gb]
+    dcn_v2_psroi_pooling_forward(input, bbox, trans, no_trans, spatial_scale, output_dim, group_size, pooled_size,
+                                 part_size, sample_per_part, trans_std) -> (output, output_count)
+    dcn_v2_psroi_pooling_backward(out_grad, input, bbox, trans, top_count, no_trans, ...) -> (grad_input, grad_trans)
 """
 from .... import ops
 
@@ -21,9 +24,13 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, ke
                                    stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group)
 
 
-def dcn_v2_psroi_pooling_forward(*args, **kwargs):
-    raise RuntimeError("dcn_v2_psroi_pooling_forward: not supported on this build (never called by MonoFlex)")
+def dcn_v2_psroi_pooling_forward(input, bbox, trans, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                                 sample_per_part, trans_std):
+    return ops.ext_dcn_v2_psroi_pooling_forward(input, bbox, trans, no_trans, spatial_scale, output_dim, group_size, pooled_size,
+                                                part_size, sample_per_part, trans_std)
 
 
-def dcn_v2_psroi_pooling_backward(*args, **kwargs):
-    raise RuntimeError("dcn_v2_psroi_pooling_backward: not supported on this build (never called by MonoFlex)")
+def dcn_v2_psroi_pooling_backward(out_grad, input, bbox, trans, top_count, no_trans, spatial_scale, output_dim, group_size, pooled_size,
+                                  part_size, sample_per_part, trans_std):
+    return ops.ext_dcn_v2_psroi_pooling_backward(out_grad, input, bbox, trans, top_count, no_trans, spatial_scale, output_dim, group_size,
+                                                 pooled_size, part_size, sample_per_part, trans_std)

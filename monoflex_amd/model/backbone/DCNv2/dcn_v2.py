@@ -1,6 +1,7 @@
-"""DCNv2 operator surface of the reference (model/backbone/DCNv2/dcn_v2.py:16-128):
-`_DCNv2` autograd Function, `dcn_v2_conv`, `DCNv2`, `DCN` -- same names, arguments and error
-behaviour, backed by the gfx950 kernels through `_ext`."""
+"""DCNv2 operator surface of the reference (model/backbone/DCNv2/dcn_v2.py:16-303):
+`_DCNv2` autograd Function, `dcn_v2_conv`, `DCNv2`, `DCN` and the pooling half `_DCNv2Pooling`,
+`dcn_v2_pooling`, `DCNv2Pooling`, `DCNPooling` -- same names, arguments and error behaviour,
+backed by the gfx950 kernels through `_ext`."""
 import math
 
 import torch
@@ -155,3 +156,72 @@ class DCN(DCNv2):
         n = self.deformable_groups * kh * kw
         offset, mask = out[:, :2 * n].contiguous(), torch.sigmoid(out[:, 2 * n:3 * n]).contiguous()
         return dcn_v2_conv(input.float(), offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation, self.deformable_groups)
+
+
+class _DCNv2Pooling(Function):
+    """Deformable position-sensitive ROI pooling (reference dcn_v2.py:132-181): differentiable in `input` and `offset`."""
+
+    @staticmethod
+    def forward(ctx, input, rois, offset, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None,
+                sample_per_part=4, trans_std=.0):
+        ctx.geometry = (int(no_trans), spatial_scale, output_dim, group_size, pooled_size,
+                        pooled_size if part_size is None else part_size, sample_per_part, trans_std)
+        output, output_count = _backend.dcn_v2_psroi_pooling_forward(input, rois, offset, *ctx.geometry)
+        ctx.save_for_backward(input, rois, offset, output_count)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        input, rois, offset, output_count = ctx.saved_tensors
+        grad_input, grad_offset = _backend.dcn_v2_psroi_pooling_backward(grad_output, input, rois, offset, output_count, *ctx.geometry)
+        return (grad_input, None, grad_offset) + (None,) * 8
+
+
+dcn_v2_pooling = _DCNv2Pooling.apply
+
+
+class DCNv2Pooling(nn.Module):
+    """Pooling with caller-supplied offsets (reference dcn_v2.py:187-220)."""
+
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None, sample_per_part=4, trans_std=.0):
+        super().__init__()
+        self.spatial_scale, self.pooled_size, self.output_dim, self.no_trans = spatial_scale, pooled_size, output_dim, no_trans
+        self.group_size = group_size
+        self.part_size = pooled_size if part_size is None else part_size
+        self.sample_per_part, self.trans_std = sample_per_part, trans_std
+
+    def _pool(self, input, rois, offset, no_trans):
+        return dcn_v2_pooling(input, rois, offset, self.spatial_scale, self.pooled_size, self.output_dim, no_trans, self.group_size,
+                              self.part_size, self.sample_per_part, self.trans_std)
+
+    def forward(self, input, rois, offset):
+        assert input.shape[1] == self.output_dim
+        return self._pool(input, rois, input.new() if self.no_trans else offset, self.no_trans)
+
+
+class DCNPooling(DCNv2Pooling):
+    """Pooling that predicts its own offsets and mask (reference dcn_v2.py:223-303): plain pooling -> three-layer MLP ->
+    (offset x, offset y, mask logit) per bin -> deformable pooling * sigmoid(mask).  The last layer starts at zero, so a fresh
+    module gives plain pooling * 0.5."""
+
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None, sample_per_part=4, trans_std=.0,
+                 deform_fc_dim=1024):
+        super().__init__(spatial_scale, pooled_size, output_dim, no_trans, group_size, part_size, sample_per_part, trans_std)
+        self.deform_fc_dim = deform_fc_dim
+        if not no_trans:
+            bins = self.pooled_size * self.pooled_size
+            self.offset_mask_fc = nn.Sequential(nn.Linear(bins * self.output_dim, self.deform_fc_dim), nn.ReLU(inplace=True),
+                                                nn.Linear(self.deform_fc_dim, self.deform_fc_dim), nn.ReLU(inplace=True),
+                                                nn.Linear(self.deform_fc_dim, bins * 3))
+            self.offset_mask_fc[4].weight.data.zero_()
+            self.offset_mask_fc[4].bias.data.zero_()
+
+    def forward(self, input, rois):
+        if self.no_trans:
+            return self._pool(input, rois, input.new(), self.no_trans)
+        n = rois.shape[0]
+        plain = self._pool(input, rois, input.new(), True)
+        offset_mask = self.offset_mask_fc(plain.view(n, -1)).view(n, 3, self.pooled_size, self.pooled_size)
+        o1, o2, mask = torch.chunk(offset_mask, 3, dim=1)
+        return self._pool(input, rois, torch.cat((o1, o2), dim=1), self.no_trans) * torch.sigmoid(mask)

@@ -794,3 +794,63 @@ def ext_dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, 
                                      _ptr(gw), _ptr(gb), B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, dg,
                                      _ptr(ws), ws.numel(), _stream()), "mfx_dcn_v2_backward")
     return [gi, goff, gm, gw, gb]
+
+
+def _psroi_operands(input, rois, offset, no_trans, output_dim, part_size):
+    """Contiguous fp32 operands and the sizes both pooling entries take; `offset` may be an empty tensor when `no_trans` (dcn_v2.py:211)."""
+    _need_cuda(input, rois, offset)
+    x, r = input.float().contiguous(), rois.float().contiguous()
+    if x.dim() != 4:
+        raise RuntimeError("dcn_v2_psroi_pooling: input must be (B, C, H, W), got %s" % (tuple(x.shape),))
+    if r.dim() != 2 or r.shape[1] != 5:
+        raise RuntimeError("dcn_v2_psroi_pooling: rois must be (N, 5) rows of (batch_index, x1, y1, x2, y2), got %s" % (tuple(r.shape),))
+    if x.shape[1] != output_dim:
+        raise RuntimeError("dcn_v2_psroi_pooling: input channels and output channels must equal (got %d channels, output_dim %d)"
+                           % (x.shape[1], output_dim))
+    if no_trans:
+        return x, r, None, 0, 2
+    t = offset.float().contiguous()
+    if t.dim() != 4 or t.shape[0] < r.shape[0] or t.shape[1] < 2 or t.shape[1] % 2 or t.shape[2] != part_size or t.shape[3] != part_size:
+        raise RuntimeError("dcn_v2_psroi_pooling: offset must be (>= %d rois, 2 * num_classes, part_size = %d, part_size), got %s"
+                           % (r.shape[0], part_size, tuple(t.shape)))
+    return x, r, t, t.shape[0], t.shape[1]
+
+
+@on_tensor_device
+def ext_dcn_v2_psroi_pooling_forward(input, rois, offset, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                                     sample_per_part, trans_std):
+    """`_ext.dcn_v2_psroi_pooling_forward` (src/dcn_v2.h:94-138) -> (output, output_count), both (N, output_dim, pooled, pooled) fp32."""
+    no_trans = int(no_trans)
+    x, r, t, trans_rois, trans_ch = _psroi_operands(input, rois, offset, no_trans, output_dim, part_size)
+    B, C, H, W = x.shape
+    N = r.shape[0]
+    out = torch.empty((N, output_dim, pooled_size, pooled_size), dtype=torch.float32, device=x.device)
+    count = torch.empty_like(out)
+    L.check(L.load().mfx_dcn_v2_psroi_pooling_forward(_ptr(x), _ptr(r), _ptr(t), _ptr(out), _ptr(count), B, C, H, W, N, trans_rois, trans_ch,
+                                                      no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                                                      sample_per_part, trans_std, _stream()), "mfx_dcn_v2_psroi_pooling_forward")
+    return out, count
+
+
+@on_tensor_device
+def ext_dcn_v2_psroi_pooling_backward(grad_output, input, rois, offset, output_count, no_trans, spatial_scale, output_dim, group_size,
+                                      pooled_size, part_size, sample_per_part, trans_std):
+    """`_ext.dcn_v2_psroi_pooling_backward` (src/dcn_v2.h:140-190) -> (grad_input, grad_offset); grad_offset has the shape of `offset`
+    (the empty tensor's when `no_trans`)."""
+    no_trans = int(no_trans)
+    _need_cuda(grad_output, output_count)
+    x, r, t, trans_rois, trans_ch = _psroi_operands(input, rois, offset, no_trans, output_dim, part_size)
+    B, C, H, W = x.shape
+    N = r.shape[0]
+    go, cnt = grad_output.float().contiguous(), output_count.float().contiguous()
+    want = (N, output_dim, pooled_size, pooled_size)
+    if tuple(go.shape) != want or tuple(cnt.shape) != want:
+        raise RuntimeError("dcn_v2_psroi_pooling_backward: grad_output / output_count must be %s, got %s / %s"
+                           % (want, tuple(go.shape), tuple(cnt.shape)))
+    gi = torch.empty_like(x)
+    goff = torch.empty_like(t) if t is not None else torch.zeros_like(offset, dtype=torch.float32)
+    L.check(L.load().mfx_dcn_v2_psroi_pooling_backward(_ptr(go), _ptr(x), _ptr(r), _ptr(t), _ptr(cnt), _ptr(gi), _ptr(goff) if t is not None else None,
+                                                       B, C, H, W, N, trans_rois, trans_ch, no_trans, spatial_scale, output_dim, group_size,
+                                                       pooled_size, part_size, sample_per_part, trans_std, _stream()),
+            "mfx_dcn_v2_psroi_pooling_backward")
+    return gi, goff
