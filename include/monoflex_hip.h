@@ -659,6 +659,17 @@ typedef struct {
 } mfx_kitti_desc;
 int mfx_kitti_encode_targets(const mfx_kitti_desc* d, void* stream);
 
+/* The same encoder with a per-sample view flag (DATASETS.USE_RIGHT_IMAGE, kitti.py:100-104, 232-252). right: (B) int32 on the
+ * device, 1 = the sample is the right colour camera's view of its frame: d->P holds P3 (kitti_utils.py:186-187 with
+ * use_right_cam) and, before anything else, every object's label 2D box is replaced by
+ *   float32([max(min_u, 0), max(min_v, 0), min(max_u, img_w - 1), min(max_v, img_h - 1)])            (kitti.py:244-249)
+ * over its eight 3D corners (kitti_utils.py:115-133) projected through the unflipped P in float64 (kitti_utils.py:316-325);
+ * Python's max / min, so a NaN passes through and no object is dropped here. The flip that may follow works on those float32
+ * scalars and rounds to float32 after every operation (augmentations.py:42-45); `gt_bboxes` stores the result. Rows with
+ * right == 0 are computed exactly as by mfx_kitti_encode_targets; right == NULL is that entry. status bits keep their meaning.
+ * The flags travel beside the descriptor so that the mfx_kitti_desc layout and MFX_ABI_VERSION stay as they are. */
+int mfx_kitti_encode_targets_views(const mfx_kitti_desc* d, const int32_t* right, void* stream);
+
 /* uint8 RGB images of different sizes (packed back to back, HWC) -> (B,3,in_h,in_w) float32 NCHW: optional left-right
  * flip, centre zero padding, /255, (x-mean)/std; the padding is zero BEFORE normalisation (kitti.py:218-228). */
 int mfx_kitti_preprocess_u8(const uint8_t* pixels, const int64_t* offsets, const int32_t* img_wh, const int32_t* flip,

@@ -12,11 +12,12 @@
 
 namespace mfx {
 
-__global__ void __launch_bounds__(64) kitti_objects_kernel(mfx_kitti_desc d) {
+__global__ void __launch_bounds__(64) kitti_objects_kernel(mfx_kitti_desc d, const int32_t* right) {
   const int b = blockIdx.x;
+  const bool right_view = right && right[b] != 0;    // uniform per block
   if (threadIdx.x == 0) kitti::image_header(d, b);
   __syncthreads();                                   // status[b] is initialised before any object ORs into it
-  for (int i = threadIdx.x; i < d.max_objs; i += blockDim.x) kitti::encode_object(d, b, i);
+  for (int i = threadIdx.x; i < d.max_objs; i += blockDim.x) kitti::encode_object(d, b, i, right_view);
   const int max_edge = 2 * (d.in_w / d.down + d.in_h / d.down);
   for (int k = threadIdx.x; k < max_edge; k += blockDim.x) kitti::edge_point(d, b, k);
 }
@@ -38,23 +39,30 @@ __global__ void __launch_bounds__(256) kitti_preprocess_kernel(const uint8_t* pi
 
 }  // namespace mfx
 
-extern "C" int mfx_kitti_encode_targets(const mfx_kitti_desc* d, void* stream) {
+// Both encoder entries: argument checks, then the object kernel (with the optional view flags) and the heat-map kernel.
+static int kitti_encode_launch(const mfx_kitti_desc* d, const int32_t* right, void* stream) {
   using namespace mfx;
-  if (!d) return mfx_fail(MFX_ERR_ARG, "mfx_kitti_encode_targets: null descriptor");
+  if (!d) return mfx_fail(MFX_ERR_ARG, "KITTI target encoder: null descriptor");
   if (d->B <= 0 || d->max_objs <= 0 || d->num_classes <= 0 || d->down <= 0 || d->in_w % d->down || d->in_h % d->down)
-    return mfx_fail(MFX_ERR_ARG, "mfx_kitti_encode_targets: bad sizes (B, max_objs, num_classes, down must be positive; input size divisible by down)");
+    return mfx_fail(MFX_ERR_ARG, "KITTI target encoder: bad sizes (B, max_objs, num_classes, down must be positive; input size divisible by down)");
   const void* ptrs[] = {d->records, d->n_obj, d->P, d->img_wh, d->flip, d->hm, d->cls_ids, d->target_centers, d->keypoints,
                         d->keypoints_depth_mask, d->dimensions, d->locations, d->reg_mask, d->reg_weight, d->offset_3D, d->bboxes,
                         d->gt_bboxes, d->rotys, d->trunc_mask, d->alphas, d->orientations, d->occlusions, d->truncations,
                         d->pad_size, d->edge_indices, d->edge_len, d->P_out, d->heat_radius, d->status};
   for (const void* p : ptrs)
-    if (!p) return mfx_fail(MFX_ERR_ARG, "mfx_kitti_encode_targets: every input and output pointer of the descriptor must be set");
+    if (!p) return mfx_fail(MFX_ERR_ARG, "KITTI target encoder: every input and output pointer of the descriptor must be set");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(kitti_objects_kernel, dim3(d->B), dim3(64), 0, st, *d);
+  hipLaunchKernelGGL(kitti_objects_kernel, dim3(d->B), dim3(64), 0, st, *d, right);
   const int out_h = d->in_h / d->down;
   hipLaunchKernelGGL(kitti_heatmap_kernel, dim3(d->B * d->num_classes * out_h), dim3(256), 0, st, *d);
   MFX_HIP_CHECK(hipGetLastError());
   return MFX_OK;
+}
+
+extern "C" int mfx_kitti_encode_targets(const mfx_kitti_desc* d, void* stream) { return kitti_encode_launch(d, nullptr, stream); }
+
+extern "C" int mfx_kitti_encode_targets_views(const mfx_kitti_desc* d, const int32_t* right, void* stream) {
+  return kitti_encode_launch(d, right, stream);
 }
 
 extern "C" int mfx_kitti_preprocess_u8(const uint8_t* pixels, const int64_t* offsets, const int32_t* img_wh, const int32_t* flip,

@@ -7,7 +7,8 @@
 //
 // dtype rules (reference data/datasets/kitti.py:334-494): python floats and projections are float64; `obj.t`, `obj.box2d`
 // and whatever is derived from them by numpy scalar arithmetic stay float32.  Compile with -ffp-contract=off: a fused
-// multiply-add would change float32 results the reference rounds twice.
+// multiply-add would change float32 results the reference rounds twice.  Right-view samples (kitti.py:232-252) carry a
+// regenerated float32 box, so their flip is a float32 chain; label text is float64 until it is stored.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -124,8 +125,43 @@ MFX_HD int intersect_center(const double pc[2], const double c2d[2], int img_w, 
 MFX_HD int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 MFX_HD int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// 8 corners of the 3D box in camera coordinates (kitti_utils.py:115-133): R(ry) . corner in float64, + float32 t
+MFX_HD void corners3d(double h, double w, double l, double ry, float t0, float t1, float t2, double (*K3)[3]) {
+  const double c = std::cos(ry), s = std::sin(ry);
+  const double xs[4] = {l / 2, l / 2, -l / 2, -l / 2}, zs[4] = {w / 2, -w / 2, -w / 2, w / 2};
+  for (int k = 0; k < 8; ++k) {
+    const double x = xs[k & 3], y = k < 4 ? 0.0 : -h, z = zs[k & 3];
+    K3[k][0] = (c * x + 0.0 * y + s * z) + (double)t0;
+    K3[k][1] = (0.0 * x + 1.0 * y + 0.0 * z) + (double)t1;
+    K3[k][2] = (-s * x + 0.0 * y + c * z) + (double)t2;
+  }
+}
+
+// Right-view 2D box (kitti.py:243-250): the eight corners of the label as read (no flip yet) through the camera matrix
+// as read, clamped to the image with Python's max / min and stored as float32.  numpy's .min() / .max() hand a NaN on,
+// and so does `max(a, 0)` (`0 > a ? 0 : a`); corners behind the camera are divided by their negative depth.
+MFX_HD void right_view_box(const double* P, double h, double w, double l, double ry, float t0, float t1, float t2,
+                           int img_w, int img_h, float box[4]) {
+  double K3[8][3];
+  corners3d(h, w, l, ry, t0, t1, t2, K3);
+  double lo_u = 0, lo_v = 0, hi_u = 0, hi_v = 0;
+  for (int k = 0; k < 8; ++k) {
+    double u, v, wq;
+    project(P, K3[k][0], K3[k][1], K3[k][2], u, v, wq);
+    if (k == 0) { lo_u = hi_u = u; lo_v = hi_v = v; continue; }
+    lo_u = (u < lo_u || u != u) ? u : lo_u;  hi_u = (u > hi_u || u != u) ? u : hi_u;
+    lo_v = (v < lo_v || v != v) ? v : lo_v;  hi_v = (v > hi_v || v != v) ? v : hi_v;
+  }
+  const double right_edge = img_w - 1, bottom_edge = img_h - 1;
+  box[0] = (float)(0.0 > lo_u ? 0.0 : lo_u);
+  box[1] = (float)(0.0 > lo_v ? 0.0 : lo_v);
+  box[2] = (float)(right_edge < hi_u ? right_edge : hi_u);
+  box[3] = (float)(bottom_edge < hi_v ? bottom_edge : hi_v);
+}
+
 // One object of one image: zeroes row i of every per-object field, then fills it unless the reference skips the object.
-MFX_HD void encode_object(const mfx_kitti_desc& d, int b, int i) {
+// right: the sample is the right-camera view (d.P holds P3): the label's 2D box is replaced by right_view_box() first.
+MFX_HD void encode_object(const mfx_kitti_desc& d, int b, int i, bool right = false) {
   const int M = d.max_objs;
   const long row = (long)b * M + i;
   d.cls_ids[row] = 0; d.reg_mask[row] = 0; d.trunc_mask[row] = 0; d.reg_weight[row] = 0.f;
@@ -154,30 +190,32 @@ MFX_HD void encode_object(const mfx_kitti_desc& d, int b, int i) {
   const double h = rec[7], w = rec[8], l = rec[9];
   float t0 = (float)rec[10]; const float t1 = (float)rec[11], t2 = (float)rec[12];
   double ry = rec[13];
+  float rbox[4] = {0.f, 0.f, 0.f, 0.f};
+  if (right) right_view_box(d.P + b * 12, h, w, l, ry, t0, t1, t2, img_w, img_h, rbox);
   if (flip) {                                                                        // augmentations.py:44-66
-    const double bw = xmax - xmin;
-    xmin = img_w - xmax - 1;
-    xmax = xmin + bw;
+    if (right) {                                                                     // the box is float32 scalars by now: every step rounds to float32
+      const float bw = rbox[2] - rbox[0];
+      rbox[0] = ((float)img_w - rbox[2]) - 1.f;
+      rbox[2] = rbox[0] + bw;
+    } else {
+      const double bw = xmax - xmin;
+      xmin = img_w - xmax - 1;
+      xmax = xmin + bw;
+    }
     ry = ry < 0 ? (-PI - ry) : (PI - ry);
     ry = wrap_pi(ry);
     t0 = -t0;
   }
-  const float lbl[4] = {(float)xmin, (float)ymin, (float)xmax, (float)ymax};
+  float lbl[4] = {(float)xmin, (float)ymin, (float)xmax, (float)ymax};
+  if (right) for (int k = 0; k < 4; ++k) lbl[k] = rbox[k];
   const double alpha = wrap_pi(ry - std::atan2((double)t0, (double)t2));
 
   const float loc1 = t1 - (float)(h / 2);                                            // float32 arithmetic (kitti.py:361)
   if (t2 <= 0.f) return;
 
   // 8 corners (kitti_utils.py:120-131) + centres of the bottom / top faces (kitti.py:397-398)
-  const double c = std::cos(ry), s = std::sin(ry);
-  const double xs[4] = {l / 2, l / 2, -l / 2, -l / 2}, zs[4] = {w / 2, -w / 2, -w / 2, w / 2};
   double K3[10][3];
-  for (int k = 0; k < 8; ++k) {
-    const double x = xs[k & 3], y = k < 4 ? 0.0 : -h, z = zs[k & 3];
-    K3[k][0] = (c * x + 0.0 * y + s * z) + (double)t0;
-    K3[k][1] = (0.0 * x + 1.0 * y + 0.0 * z) + (double)t1;
-    K3[k][2] = (-s * x + 0.0 * y + c * z) + (double)t2;
-  }
+  corners3d(h, w, l, ry, t0, t1, t2, K3);
   for (int a = 0; a < 3; ++a) {
     K3[8][a] = (((K3[0][a] + K3[1][a]) + K3[2][a]) + K3[3][a]) / 4;
     K3[9][a] = (((K3[4][a] + K3[5][a]) + K3[6][a]) + K3[7][a]) / 4;

@@ -1,14 +1,16 @@
 """KITTI dataset front (reference data/datasets/kitti.py:28-525).
 
-Same constructor, directory layout (image_2 / label_2 / calib / ImageSets/<split>.txt), `__len__` and
+Same constructor, directory layout (image_2 [/ image_3] / label_2 / calib / ImageSets/<split>.txt), `__len__` and
 `__getitem__ -> (image, target, original_idx)` contract as the reference, with the work split differently: the host reads
 and parses files (PNG decode, label and calib text) and tosses the flip coin; padding, flipping, normalisation, all
 geometry, the Gaussian heat maps and the border walk run on the GPU (mfx_kitti_encode_targets /
 mfx_kitti_preprocess_u8), a whole batch per launch.  `load_raw` + `encode_batch` is the batch path the collator uses;
-`__getitem__` is the same thing for a batch of one.
+`__getitem__` is the same thing for a batch of one.  With DATASETS.USE_RIGHT_IMAGE (training only, kitti.py:100-104,
+232-252) index i >= N is frame i % N seen by the right colour camera: image_3/, calibration P3, the same labels, 2D boxes
+regenerated on the device from the 3D corners.
 
 Differences from the reference, by design: tensors in the target live on the device; `ori_img` (a uint8 copy of the padded
-frame kept for visualisation) is not produced; USE_RIGHT_IMAGE is not implemented (runs/monoflex.yaml: False)."""
+frame kept for visualisation) is not produced."""
 import os
 import random
 
@@ -25,11 +27,12 @@ TARGET_ORDER = ("cls_ids", "target_centers", "keypoints", "keypoints_depth_mask"
 
 
 class RawSample:
-    """What the host produces per sample: decoded frame, label records, camera matrix, flip decision."""
-    __slots__ = ("frame", "records", "calib", "flip", "original_idx")
+    """What the host produces per sample: decoded frame, label records, camera matrix, flip decision, which camera."""
+    __slots__ = ("frame", "records", "calib", "flip", "original_idx", "right")
 
-    def __init__(self, frame, records, calib, flip, original_idx):
+    def __init__(self, frame, records, calib, flip, original_idx, right=False):
         self.frame, self.records, self.calib, self.flip, self.original_idx = frame, records, calib, flip, original_idx
+        self.right = right
 
 
 class KITTIDataset(torch.utils.data.Dataset):
@@ -48,8 +51,10 @@ class KITTIDataset(torch.utils.data.Dataset):
         self.label_files = [i.replace(".png", ".txt") for i in self.image_files]
         self.classes = tuple(cfg.DATASETS.DETECT_CLASSES)
         self.num_classes, self.num_samples = len(self.classes), len(self.image_files)
-        if cfg.DATASETS.USE_RIGHT_IMAGE and is_train:
-            raise NotImplementedError("DATASETS.USE_RIGHT_IMAGE is not implemented in this build")
+        self.image_right_dir = os.path.join(root, "image_3")
+        self.use_right_img = bool(cfg.DATASETS.USE_RIGHT_IMAGE) and is_train                   # kitti.py:56
+        if self.use_right_img and not os.path.isdir(self.image_right_dir):
+            raise FileNotFoundError("DATASETS.USE_RIGHT_IMAGE needs the right-camera frames, dir = {}".format(self.image_right_dir))
         self.params = EncodeParams.from_cfg(cfg)
         self.flip_p = float(cfg.INPUT.AUG_PARAMS[0][0]) if (is_train and augment) else 0.0      # augmentations/__init__.py:15-23
         self.pixel_mean, self.pixel_std = tuple(cfg.INPUT.PIXEL_MEAN), tuple(cfg.INPUT.PIXEL_STD)
@@ -64,12 +69,16 @@ class KITTIDataset(torch.utils.data.Dataset):
         self.device = torch.device(device)
 
     def __len__(self):
-        return self.num_samples
+        return self.num_samples * 2 if self.use_right_img else self.num_samples                # kitti.py:100-104
 
     # ---- host side: files -> raw sample -------------------------------------------------------------------
     def get_image(self, idx):
         from PIL import Image
         return np.asarray(Image.open(os.path.join(self.image_dir, self.image_files[idx])).convert("RGB"), dtype=np.uint8)
+
+    def get_right_image(self, idx):
+        from PIL import Image
+        return np.asarray(Image.open(os.path.join(self.image_right_dir, self.image_files[idx])).convert("RGB"), dtype=np.uint8)
 
     def get_calibration(self, idx, use_right_cam=False):
         return Calibration(os.path.join(self.calib_dir, self.label_files[idx]), use_right_cam=use_right_cam)
@@ -91,11 +100,16 @@ class KITTIDataset(torch.utils.data.Dataset):
         return torch.tensor(pts, dtype=torch.int64).reshape(-1, 2)
 
     def load_raw(self, idx):
-        if idx >= self.num_samples:
+        if idx < 0:
+            idx = idx + len(self)                                             # from the end, as a sequence would
+        if not 0 <= idx < len(self):
             raise IndexError(idx)
+        right = bool(idx >= self.num_samples)                               # kitti.py:232-239
+        idx = idx % self.num_samples
+        frame = self.get_right_image(idx) if right else self.get_image(idx)
         flip = self.flip_p > 0 and random.random() < self.flip_p            # augmentations.py:38
-        return RawSample(self.get_image(idx), self.get_label_objects(idx), self.get_calibration(idx), bool(flip),
-                         self.image_files[idx][:6])
+        return RawSample(frame, self.get_label_objects(idx), self.get_calibration(idx, use_right_cam=right), bool(flip),
+                         self.image_files[idx][:6], right)
 
     # ---- device side: raw samples -> network input + targets ----------------------------------------------
     def encode_batch(self, samples, check=True):
@@ -104,8 +118,9 @@ class KITTIDataset(torch.utils.data.Dataset):
         flips = [s.flip for s in samples]
         sizes = [(f.shape[1], f.shape[0]) for f in frames]
         images = preprocess_images(frames, flips, self.params, self.device, self.pixel_mean, self.pixel_std)
+        views = dict(rights=[s.right for s in samples]) if self.use_right_img else {}
         fields = encode_targets([s.records for s in samples], [s.calib.P for s in samples], sizes, flips, self.params,
-                                self.device, check=check)
+                                self.device, check=check, **views)
         test_split = self.split == "test"
         targets = []
         for b, s in enumerate(samples):

@@ -1,4 +1,4 @@
-"""Device-side sample encoding: the ctypes front of mfx_kitti_encode_targets / mfx_kitti_preprocess_u8.
+"""Device-side sample encoding: the ctypes front of mfx_kitti_encode_targets[_views] / mfx_kitti_preprocess_u8.
 
 Replaces the numeric half of the reference's KITTIDataset.__getitem__ (data/datasets/kitti.py:231-525), its flip
 augmentation (data/augmentations/augmentations.py:33-78) and ToTensor+Normalize (data/transforms/transforms.py:15-31):
@@ -126,29 +126,50 @@ def _alloc_outputs(B, dims, device):
     return {name: _view(buf, o, full, dt) for name, (o, full, dt) in specs.items()}
 
 
-def encode_targets(records, Ps, sizes, flips, params, device, check=True):
+class PreparedEncode:
+    """One batch ready to launch: inputs uploaded, outputs allocated, descriptor filled. `launch()` enqueues the two encoder
+    kernels on the current stream and may be repeated (the timing tools do); `out` is {field: (B, ...) device tensor}."""
+
+    def __init__(self, records, Ps, sizes, flips, params, device, rights=None):
+        self.lib, self.device = L.load(), device
+        arrays = pack_inputs(records, Ps, sizes, flips, params)
+        B, dims = len(records), params.dims()
+        if rights is not None:
+            arrays["right"] = np.asarray(rights, dtype=np.int32).reshape(B).copy()      # rides in the same pinned upload as `flip`
+        self.inp = _upload(arrays, device)
+        self.right = self.inp.pop("right", None)
+        self.out = _alloc_outputs(B, dims, device)
+        d = self.desc = L.KittiDesc()
+        for k, t in self.inp.items():
+            setattr(d, k, t.data_ptr())
+        for name, (member, _, _) in TARGET_FIELDS.items():
+            setattr(d, member, self.out[name].data_ptr())
+        d.B, d.max_objs, d.in_w, d.in_h, d.down, d.num_classes = B, params.max_objs, params.in_w, params.in_h, params.down, params.num_classes
+        d.filter_trunc, d.filter_size, d.edge_ratio = params.filter_trunc, params.filter_size, params.edge_ratio
+
+    def launch(self):
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if self.right is None:
+                L.check(self.lib.mfx_kitti_encode_targets(ctypes.byref(self.desc), stream), "mfx_kitti_encode_targets")
+            else:
+                L.check(self.lib.mfx_kitti_encode_targets_views(ctypes.byref(self.desc), self.right.data_ptr(), stream),
+                        "mfx_kitti_encode_targets_views")
+
+
+def encode_targets(records, Ps, sizes, flips, params, device, check=True, rights=None):
     """Batch of raw labels -> {field: (B, ...) device tensor} with every field of the reference's training target
     (kitti.py:496-523; "calib" is left to the caller, "P" is the camera matrix after the flip).
+    rights: per-sample flags, 1 = right-camera view (DATASETS.USE_RIGHT_IMAGE, kitti.py:232-252): `Ps` holds P3 for that
+    sample and its 2D boxes are regenerated from the 3D corners (mfx_kitti_encode_targets_views). None = all left views.
     check=True synchronises once to turn a non-zero status into the exception the reference would have raised."""
     if torch.device(device).type != "cuda":
         raise RuntimeError("encode_targets runs on the GPU (HIP kernels); there is no CPU fallback")
-    lib = L.load()
-    inp = _upload(pack_inputs(records, Ps, sizes, flips, params), device)
-    B, dims = len(records), params.dims()
-    out = _alloc_outputs(B, dims, device)
-    d = L.KittiDesc()
-    for k, t in inp.items():
-        setattr(d, k, t.data_ptr())
-    for name, (member, _, _) in TARGET_FIELDS.items():
-        setattr(d, member, out[name].data_ptr())
-    d.B, d.max_objs, d.in_w, d.in_h, d.down, d.num_classes = B, params.max_objs, params.in_w, params.in_h, params.down, params.num_classes
-    d.filter_trunc, d.filter_size, d.edge_ratio = params.filter_trunc, params.filter_size, params.edge_ratio
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream().cuda_stream
-        L.check(lib.mfx_kitti_encode_targets(ctypes.byref(d), ctypes.c_void_p(stream)), "mfx_kitti_encode_targets")
+    prepared = PreparedEncode(records, Ps, sizes, flips, params, device, rights)
+    prepared.launch()
     if check:
-        check_status(out["status"])
-    return out
+        check_status(prepared.out["status"])
+    return prepared.out
 
 
 def check_status(status):

@@ -20,6 +20,8 @@ import torch
 KITTI_P2 = np.array([[721.5377, 0.0, 609.5593, 44.85728],
                      [0.0, 721.5377, 172.854, 0.2163791],
                      [0.0, 0.0, 1.0, 0.002745884]], dtype=np.float64)
+KITTI_P3 = KITTI_P2.copy()                                           # the right colour camera: KITTI's usual P3 offsets
+KITTI_P3[:, 3] = (-339.5242, 2.199936, 0.002729905)
 
 
 def _gen(seed):
