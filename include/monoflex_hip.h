@@ -59,6 +59,7 @@ const char* mfx_last_error(void);
  * (other values return MFX_ERR_ARG and leave the switch unchanged),
  * "wgrad_*" / "dcn_wgrad_m" (training GEMM partitioning), "heads_persist" (1 = one workgroup per resident slot over (tile, branch)
  * unit ranges, n > 1 = n workgroups, 0 = one workgroup per tile), "heads_planes", "heads_dbg" (timing probes: wrong results).
+ * The complete list of switches and counters, with defaults and value rules: monoflex_amd/csrc/options.h.
  * Unknown names return MFX_ERR_ARG. */
 int mfx_set_option(const char* name, int value);
 /* every switch back to its load-time value (what a test harness calls between tests) */

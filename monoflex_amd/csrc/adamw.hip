@@ -11,8 +11,6 @@
 #include "err.h"
 #include "common.h"
 
-extern long g_cnt_adamw_multi;      // dispatch counter (conv_kernels.hip, mfx_get_counter)
-
 namespace mfx {
 
 constexpr int AW_CHUNK = 4096;

@@ -1,10 +1,9 @@
 // ABI version + error string plumbing of libmonoflex_hip.so.
 #include "../../include/monoflex_hip.h"
 #include "err.h"
+#include "internal.h"
 #include <cstdio>
 #include <cstring>
-
-int g_opt_det = 0;
 
 static thread_local char g_err[512] = "";
 
@@ -19,9 +18,7 @@ int mfx_fail_hip(hipError_t e, const char* what) {
 extern "C" const char* mfx_last_error(void) { return g_err; }
 extern "C" int mfx_abi_version(void) { return MFX_ABI_VERSION; }
 
-// split-precision range sentinel: the per-translation-unit flags of common.h's lds_operand<f32s_t>
-int mfx_range_flag_conv_halo(int), mfx_range_flag_conv_kernels(int), mfx_range_flag_dcn_wave(int), mfx_range_flag_f1_fused(int), mfx_range_flag_heads(int),
-    mfx_range_flag_stem(int), mfx_range_flag_dcn_lds(int), mfx_range_flag_conv_cws(int);
+// split-precision range sentinel: ORs the per-translation-unit flags (internal.h)
 extern "C" int mfx_f16x2_range_check(int reset) {
     int (*const f[])(int) = {mfx_range_flag_conv_halo, mfx_range_flag_conv_kernels, mfx_range_flag_dcn_wave, mfx_range_flag_f1_fused, mfx_range_flag_heads,
                              mfx_range_flag_stem, mfx_range_flag_dcn_lds, mfx_range_flag_conv_cws};

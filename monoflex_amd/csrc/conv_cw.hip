@@ -26,6 +26,7 @@
 // Reference layers: model/backbone/dla_dcn.py:84-98 (BasicBlock conv1 / conv2 of levels 2-5), 246-259 (Tree).
 #include "../../include/monoflex_hip.h"
 #include "err.h"
+#include "internal.h"
 #include "igemm.h"
 #include <type_traits>
 
@@ -306,8 +307,6 @@ __global__ __launch_bounds__(WN * WK * 64, OCC) void conv3x3_cw_kernel(const T* 
     }
 }
 
-int g_opt_halo_cw = 1;       // option "halo_cw": 0 = conv3x3_wave_kernel only, 1 = this kernel where an instantiation exists
-
 template <typename T, typename TO, int CG, int CT, int WN, int FN, int WK, int OCC, int S = 1, int ROWS = kCwRows, bool ST = false>
 static int launch_cw(const mfx_conv_desc* d, hipStream_t st) {
     using SM = CwSmem<CG, WN, FN, WK, S, ROWS>;
@@ -332,7 +331,6 @@ static int launch_cw(const mfx_conv_desc* d, hipStream_t st) {
     return MFX_OK;
 }
 
-int g_opt_cw_rows6 = 1;      // option "cw_rows6": 0 = 8-row tiles everywhere
 static inline bool cw_rows6(const mfx_conv_desc* d) { return g_opt_cw_rows6 && d->Ho % 6 == 0 && d->Ho % 8 != 0 && d->Ho <= 48; }
 
 template <typename T, int OCC> static int cw_shape(const mfx_conv_desc* d, int v, hipStream_t st) {

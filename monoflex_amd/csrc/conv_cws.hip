@@ -12,6 +12,7 @@
 // Reference layers: model/backbone/dla_dcn.py:84-98 (BasicBlock conv1 / conv2 of levels 2-5), DCNv2/dcn_v2.py:118-122 (the 27-channel offset / mask convs).
 #include "../../include/monoflex_hip.h"
 #include "err.h"
+#include "internal.h"
 #include "igemm.h"
 #include <type_traits>
 
@@ -269,8 +270,6 @@ __global__ __launch_bounds__(WN * WK * 64, 2) void conv3x3_cws_kernel(const floa
         __builtin_amdgcn_wave_barrier();
     }
 }
-
-int g_opt_halo_cws = 1;      // option "halo_cws": 0 = conv3x3_wave_kernel<f32s_t> only, 1 = this kernel where an instantiation exists
 
 template <int CT, int WN, int FN, int WK, int ROWS = 8>
 static int launch_cws(const mfx_conv_desc* d, hipStream_t st) {

@@ -17,12 +17,11 @@
 //     barrier) so stores and residual loads are 16 bytes per lane along channels.
 #include "../../include/monoflex_hip.h"
 #include "err.h"
+#include "internal.h"
 #include "igemm.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
-
-extern long g_cnt_conv_cw, g_cnt_conv_cws, g_cnt_conv_halo;     // dispatch counters (conv_kernels.hip, mfx_get_counter)
 
 namespace mfx {
 
@@ -420,16 +419,8 @@ apply_act_chunk<OE>(v, ep.act, gn);
 static inline int cdivh(int a, int b) { return (a + b - 1) / b; }
 static inline int ilog2h(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-int g_opt_halo = 1;          // 0 = generic kernel only, 1 = automatic, >= 2 = force variant (value - 1)
-int g_opt_halo_cg = 0;       // max channels per patch pass (0 = default)
-int g_opt_halo_s2 = 1;       // option "halo_s2": 0 = stride-2 3x3 convs stay on the generic implicit-GEMM kernel
-int g_opt_halo_pair = 1;     // option "halo_pair": split precision walks K in step pairs where mfx_conv_desc.w_frag_pair is given (0 = two mma_chunk per pair)
-
 template <typename T, typename TO, int WN, int FN, int WK = 1, bool ST = false>
 static int launch_halo_st(const mfx_conv_desc* d, hipStream_t st);
-
-int try_conv_cw(const mfx_conv_desc* d, int v, hipStream_t st);      // conv_cw.hip: 0 = ran, 1 = no instantiation, < 0 = error
-int try_conv_cws(const mfx_conv_desc* d, int v, hipStream_t st);     // conv_cws.hip: the same for split precision
 
 static bool g_halo_stats_ran = false;    // set by the launch that ran a statistics-accumulating instantiation (read by try_conv_halo)
 

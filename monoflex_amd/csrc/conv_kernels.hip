@@ -2,10 +2,8 @@
 // modulated deformable convolution.  All share igemm.h's LDS-tiled MFMA main loop and epilogue.
 #include "../../include/monoflex_hip.h"
 #include "err.h"
+#include "internal.h"
 #include "igemm.h"
-#include <string>
-#include <utility>
-#include <vector>
 #include <type_traits>
 
 namespace mfx {
@@ -292,41 +290,6 @@ static inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; 
 static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-int try_conv_halo(const mfx_conv_desc* d, hipStream_t st, int* stats_ran);   // conv_halo.hip
-extern int g_opt_halo_cw, g_opt_cw_rows6, g_opt_halo_cws;
-extern int g_opt_halo, g_opt_halo_cg, g_opt_halo_pair, g_opt_halo_s2, g_opt_dcn_wave, g_opt_dcn_patch, g_opt_dcn_patch_fn8, g_opt_dcn_wgrad_m;
-}
-extern long g_cnt_dcn_bt_fused, g_cnt_dcn_bt_fly;
-// dispatch counters (mfx_get_counter): launches of each kernel family mfx_dcn_nhwc / mfx_conv2d_nhwc chose, since process start
-long g_cnt_dcn_lds = 0, g_cnt_dcn_lds_of = 0, g_cnt_dcn_lds_split = 0, g_cnt_dcn_patch = 0, g_cnt_dcn_wave = 0, g_cnt_dcn_gather = 0;
-long g_cnt_conv_cw = 0, g_cnt_conv_cws = 0, g_cnt_conv_halo = 0, g_cnt_conv_igemm = 0, g_cnt_conv_splitk = 0;
-// training-side families (incremented in train_kernels.hip, wgrad_tr.hip, gram_heads.hip, adamw.hip; conv_bn_stats here)
-long g_cnt_wgrad_patch = 0, g_cnt_wgrad_tr = 0, g_cnt_wgrad_mfma = 0, g_cnt_wgrad_valu = 0, g_cnt_wgrad_reduce = 0, g_cnt_stem_wgrad = 0;
-long g_cnt_bn_fwd_onepass = 0, g_cnt_bn_bwd_onepass = 0, g_cnt_bn_fwd_two = 0, g_cnt_bn_bwd_two = 0, g_cnt_conv_bn_stats = 0;
-long g_cnt_gram = 0, g_cnt_adamw_multi = 0;
-extern long g_cnt_dcn_bt_tile, g_cnt_dcn_bt_sample, g_cnt_dcn_bt_far;
-extern int g_opt_ext_bwd_fast;
-extern int g_opt_dcn_bt_fly;
-extern int g_opt_wgrad_min_m;
-extern int g_opt_dcn_bt_gcol_as;
-extern int g_opt_dcn_bt_fly_bias;
-extern int g_opt_dcn_bt_fuse_min_chunks, g_opt_dcn_bt_fuse_blocks, g_opt_dcn_bt_fuse_wgrad, g_opt_heads_planes, g_opt_heads_persist, g_opt_heads_dbg, g_opt_heads_mfma32, g_opt_dcn_bt_cs, g_opt_dcn_bt_cs_wgs, g_opt_dcn_bt_dbg, g_opt_wgrad_tr, g_opt_wgrad_tr_blocks, g_opt_bn_blocks, g_opt_bn_apply_blocks, g_opt_bn_onepass, g_opt_bn_onepass_grid, g_opt_bn_onepass_min_chunks, g_opt_bn_onepass_fwd_min_chunks, g_opt_wgrad_patch, g_opt_wgrad_patch_blocks, g_opt_wgrad_patch_waves;
-extern int g_opt_topk_strips, g_opt_topk_merge_z, g_opt_topk_merge_threads;                                                                                           // decode.hip (global namespace)
-extern int g_opt_wgrad_mfma, g_opt_wgrad_blocks, g_opt_wgrad_ws, g_opt_wgrad_ws_blocks;                                   // train_kernels.hip (global namespace)
-namespace mfx {
-int try_dcn_wave(const mfx_dcn_desc* d, hipStream_t st);      // dcn_wave.hip
-int try_dcn_patch(const mfx_dcn_desc* d, hipStream_t st);     // dcn_patch.hip
-int try_dcn_lds(const mfx_dcn_desc* d, hipStream_t st);       // dcn_lds.hip
-bool dcn_lds_fuses_offset_conv(const mfx_dcn_desc* d);
-extern int g_opt_dcn_lds, g_opt_dcn_lds_rows;
-bool dcn_patch_fuses_offset_conv(const mfx_dcn_desc* d);
-extern int g_opt_dcn_fuse_off;
-
-// tuning overrides (mfx_set_option): 0 = automatic
-int g_opt_conv_tile = 0, g_opt_dcn_tile = 0, g_opt_cat_tile = 0, g_opt_kc = 0;
-int g_opt_ksplit = 0;        // 0 = automatic, 1 = never split, n = force n splits where legal
-int g_opt_dcn_ksplit = 0;    // same for the fused DCN kernel
-
 template <typename K> static int set_smem(K k, int smem) {
     if (smem > 64 * 1024) MFX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     return MFX_OK;
@@ -437,89 +400,6 @@ static int dispatch_conv(const mfx_conv_desc* d, const ConvGeom& g, const EpiArg
 
 using namespace mfx;
 
-// option name -> the process-wide switch it sets (nullptr: unknown)
-static int* option_slot(const std::string& n) {
-    static const std::pair<const char*, int*> table[] = {
-        {"conv_tile", &g_opt_conv_tile}, {"dcn_tile", &g_opt_dcn_tile}, {"cat_tile", &g_opt_cat_tile}, {"kc", &g_opt_kc}, {"ksplit", &g_opt_ksplit},
-        {"dcn_ksplit", &g_opt_dcn_ksplit}, {"wgrad_mfma", &g_opt_wgrad_mfma}, {"wgrad_blocks", &g_opt_wgrad_blocks}, {"wgrad_ws", &g_opt_wgrad_ws},
-        {"wgrad_ws_blocks", &g_opt_wgrad_ws_blocks}, {"dcn_wgrad_m", &g_opt_dcn_wgrad_m}, {"halo", &g_opt_halo}, {"halo_cg", &g_opt_halo_cg},
-        {"halo_cw", &g_opt_halo_cw}, {"halo_cws", &g_opt_halo_cws}, {"ext_bwd_fast", &g_opt_ext_bwd_fast}, {"cw_rows6", &g_opt_cw_rows6}, {"halo_pair", &g_opt_halo_pair}, {"halo_s2", &g_opt_halo_s2}, {"dcn_wave", &g_opt_dcn_wave}, {"dcn_patch", &g_opt_dcn_patch}, {"dcn_lds", &g_opt_dcn_lds}, {"dcn_lds_rows", &g_opt_dcn_lds_rows},
-        {"dcn_patch_fn8", &g_opt_dcn_patch_fn8}, {"dcn_fuse_off", &g_opt_dcn_fuse_off}, {"topk_strips", &g_opt_topk_strips}, {"topk_merge_z", &g_opt_topk_merge_z}, {"topk_merge_threads", &g_opt_topk_merge_threads},
-#ifdef MFX_PROBES
-        {"dcn_bt_dbg", &g_opt_dcn_bt_dbg}, {"heads_dbg", &g_opt_heads_dbg},
-#endif
-        {"wgrad_tr", &g_opt_wgrad_tr}, {"bn_blocks", &g_opt_bn_blocks}, {"heads_planes", &g_opt_heads_planes}, {"heads_mfma32", &g_opt_heads_mfma32}, {"heads_persist", &g_opt_heads_persist},
-        {"dcn_bt_fuse_wgrad", &g_opt_dcn_bt_fuse_wgrad}, {"dcn_bt_fly", &g_opt_dcn_bt_fly}, {"dcn_bt_gcol_as", &g_opt_dcn_bt_gcol_as}, {"dcn_bt_fly_bias", &g_opt_dcn_bt_fly_bias}, {"wgrad_min_m", &g_opt_wgrad_min_m}, {"dcn_bt_fuse_blocks", &g_opt_dcn_bt_fuse_blocks},
-        {"deterministic", &g_opt_det}, {"dcn_bt_fuse_min_chunks", &g_opt_dcn_bt_fuse_min_chunks}, {"dcn_bt_cs", &g_opt_dcn_bt_cs},
-        {"dcn_bt_cs_wgs", &g_opt_dcn_bt_cs_wgs}, {"bn_apply_blocks", &g_opt_bn_apply_blocks}, {"bn_onepass", &g_opt_bn_onepass}, {"bn_onepass_grid", &g_opt_bn_onepass_grid}, {"bn_onepass_min_chunks", &g_opt_bn_onepass_min_chunks}, {"bn_onepass_fwd_min_chunks", &g_opt_bn_onepass_fwd_min_chunks}, {"wgrad_patch", &g_opt_wgrad_patch},
-        {"wgrad_patch_waves", &g_opt_wgrad_patch_waves}, {"wgrad_patch_blocks", &g_opt_wgrad_patch_blocks}, {"wgrad_tr_blocks", &g_opt_wgrad_tr_blocks}};
-    for (const auto& e : table)
-        if (n == e.first) return e.second;
-    return nullptr;
-}
-
-// the value every switch had before anyone touched it (recorded at the first mfx_set_option of that switch): mfx_reset_options() puts them back
-static std::vector<std::pair<int*, int>>& option_defaults() { static std::vector<std::pair<int*, int>> v; return v; }
-
-extern "C" int mfx_set_option(const char* name, int value) {
-    if (!name) return mfx_fail(MFX_ERR_ARG, "set_option: null name");
-    const std::string n(name);
-#ifndef MFX_PROBES
-    if (n == "dcn_bt_dbg" || n == "heads_dbg")
-        return mfx_fail(MFX_ERR_UNSUPPORTED, "set_option: timing-probe switches (wrong results by design) exist in probe builds only: MFX_PROBES=1 python -m monoflex_amd.build");
-#endif
-    int* slot = option_slot(n);
-    if (!slot) return mfx_fail(MFX_ERR_ARG, "set_option: unknown option");
-    if (n == "topk_merge_threads" && (value < 64 || value > 512 || value % 64 != 0))      // the merge ranks by whole wavefronts; 512 = its __launch_bounds__
-        return mfx_fail(MFX_ERR_ARG, "set_option: topk_merge_threads must be a multiple of 64 in 64..512");
-    if (n == "topk_merge_z" && (value < 1 || value > 64)) return mfx_fail(MFX_ERR_ARG, "set_option: topk_merge_z must be in 1..64");
-    auto& defs = option_defaults();
-    bool seen = false;
-    for (const auto& e : defs) seen = seen || e.first == slot;
-    if (!seen) defs.emplace_back(slot, *slot);
-    if (n == "dcn_wgrad_m") value = value < 64 ? 64 : value;
-    else if (n == "dcn_bt_fuse_blocks") value = value > 0 ? value : 170;
-    else if (n == "deterministic") value = value ? 1 : 0;
-    else if (n == "dcn_bt_fuse_min_chunks" || n == "wgrad_patch_blocks" || n == "wgrad_tr_blocks") value = value < 1 ? 1 : value;
-    *slot = value;
-    return MFX_OK;
-}
-
-// Every tuning / debug switch back to the value it had at load time.  The switches are process-wide (one host thread drives the library:
-// see the threading note in the header), so a test that forces a kernel variant and fails half-way would otherwise leak it into the next test
-// (tests/conftest.py calls this after every GPU test).
-extern "C" int mfx_reset_options(void) {
-    for (const auto& e : option_defaults()) *e.first = e.second;
-    return MFX_OK;
-}
-
-// The CURRENT values become the ones mfx_reset_options() restores.  The host calls this once after it has applied the process's own switches
-// (MFX_OPTIONS in the environment, monoflex_amd/lib.py), so that "load-time value" means "after the environment" and an `MFX_OPTIONS=... pytest`
-// sweep keeps its switches across the per-test resets.
-extern "C" int mfx_commit_options(void) {
-    for (auto& e : option_defaults()) e.second = *e.first;
-    return MFX_OK;
-}
-
-extern "C" long mfx_get_counter(const char* name) {
-    if (!name) return mfx_fail(MFX_ERR_ARG, "get_counter: null name");
-    const std::string n(name);
-    if (n == "dcn_bt_fused") return g_cnt_dcn_bt_fused;
-    if (n == "dcn_bt_fly") return g_cnt_dcn_bt_fly;
-    static const std::pair<const char*, const long*> dispatch[] = {
-        {"dcn_lds", &g_cnt_dcn_lds}, {"dcn_lds_of", &g_cnt_dcn_lds_of}, {"dcn_lds_split", &g_cnt_dcn_lds_split}, {"dcn_patch", &g_cnt_dcn_patch},
-        {"dcn_wave", &g_cnt_dcn_wave}, {"dcn_gather", &g_cnt_dcn_gather}, {"conv_cw", &g_cnt_conv_cw}, {"conv_cws", &g_cnt_conv_cws},
-        {"conv_halo", &g_cnt_conv_halo}, {"conv_igemm", &g_cnt_conv_igemm}, {"conv_splitk", &g_cnt_conv_splitk},
-        {"wgrad_patch", &g_cnt_wgrad_patch}, {"wgrad_tr", &g_cnt_wgrad_tr}, {"wgrad_mfma", &g_cnt_wgrad_mfma}, {"wgrad_valu", &g_cnt_wgrad_valu},
-        {"wgrad_reduce", &g_cnt_wgrad_reduce}, {"stem_wgrad", &g_cnt_stem_wgrad}, {"bn_fwd_onepass", &g_cnt_bn_fwd_onepass},
-        {"bn_bwd_onepass", &g_cnt_bn_bwd_onepass}, {"bn_fwd_two", &g_cnt_bn_fwd_two}, {"bn_bwd_two", &g_cnt_bn_bwd_two},
-        {"conv_bn_stats", &g_cnt_conv_bn_stats}, {"dcn_bt_tile", &g_cnt_dcn_bt_tile}, {"dcn_bt_sample", &g_cnt_dcn_bt_sample},
-        {"dcn_bt_far", &g_cnt_dcn_bt_far}, {"gram", &g_cnt_gram}, {"adamw_multi", &g_cnt_adamw_multi}};
-    for (const auto& e : dispatch)
-        if (n == e.first) return *e.second;
-    return mfx_fail(MFX_ERR_ARG, "get_counter: unknown counter");
-}
-
 extern "C" int mfx_conv2d_nhwc(const mfx_conv_desc* d, void* stream) {
     if (!d || !d->x || !d->w || !d->y) return mfx_fail(MFX_ERR_ARG, "conv2d: null pointer");
     const bool f32like = d->dtype == MFX_F32 || d->dtype == MFX_F16X2;      // fp32 storage (F16X2: split-precision MFMA operands)
@@ -540,7 +420,7 @@ extern "C" int mfx_conv2d_nhwc(const mfx_conv_desc* d, void* stream) {
         return mfx_fail(MFX_ERR_ARG, "conv2d: output statistics need stats_done and a plain (no residual / activation / row map) epilogue");
     if (d->stats_done) *d->stats_done = 0;
     mfx_conv_desc det_copy;
-    if (g_opt_det && d->stats) {                            // epilogue statistics are one atomic per column and wave: the BN runs its own (ordered) pass
+    if (g_opt_deterministic && d->stats) {                            // epilogue statistics are one atomic per column and wave: the BN runs its own (ordered) pass
         det_copy = *d; det_copy.stats = nullptr; det_copy.stats_done = nullptr; d = &det_copy;
     }
     {

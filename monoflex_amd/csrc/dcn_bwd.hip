@@ -12,6 +12,7 @@
 #include "../../include/monoflex_hip.h"
 #include "common.h"
 #include "err.h"
+#include "internal.h"
 #include "fill.h"
 #include <type_traits>
 
@@ -96,8 +97,6 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_kernel(const T* x, const f
         }
     }
 }
-
-int g_opt_dcn_wgrad_m = 512;    // option "dcn_wgrad_m": pixels per workgroup slab of the DCN weight-gradient kernel (step: 512 -> 73.1 ms, 2048 -> 73.8, 8192 -> 83.6)
 
 // grad_weight[o][k] += sum over a slab of pixels of go[m][o] * col[m][k]; col re-sampled into LDS.
 // Block = 64 k x 64 o output tile, 256 threads each owning a 4x4 register block.
@@ -288,12 +287,8 @@ static int dcn_bwd_core(const T* x, const float* om, const T* wT, const T* go, T
 // tile-owned second-generation kernels (dcn_bwd_tile.hip: d(columns) GEMM on the matrix cores, grad_input gathered per tile in LDS instead of scattered with
 // global atomics, weight gradient as an MFMA GEMM) behind the same NCHW boundary; d_raw's mask channels are asked for as the gradient of the mask ITSELF
 // (BtGeom.raw_mask): `_ext` takes the mask as an input and knows nothing of the sigmoid in front of it (src/dcn_v2.h:48-59).
-int g_opt_ext_bwd_fast = 1;  // option "ext_bwd_fast": 0 = the first-generation scatter backward for every geometry
-extern "C" size_t mfx_dcn_backward_v2_workspace_bytes(int B, int C, int H, int W, int Cout, int dtype);
-int mfx_internal_dcn_backward_v2_f32_rawmask(const float* x, const float* offmask, const float* weight_oihw, const float* dy, float* dx, float* d_raw,
-                                             float* dweight, float* dbias, int B, int C, int H, int W, int Cout, void* workspace, size_t workspace_bytes, void* stream);
 static bool ext_bwd_fast_ok(int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw) {
-    return g_opt_ext_bwd_fast && !g_opt_det && kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && C >= 64 && (C & (C - 1)) == 0 &&
+    return g_opt_ext_bwd_fast && !g_opt_deterministic && kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && C >= 64 && (C & (C - 1)) == 0 &&
            Cout >= 64 && (Cout & (Cout - 1)) == 0 && H < 4096 && W < 4096 && (long)B * H * W < (1L << 31) / 32;
 }
 struct FastLayout { size_t x, om, go, gx, gom, v2, total; };
@@ -320,8 +315,6 @@ extern "C" size_t mfx_dcn_v2_backward_workspace_bytes_(int B, int C, int H, int 
     const size_t fast = fast_layout(B, Cp2, H, W, Cout).total;
     return fast > slow ? fast : slow;
 }
-
-int mfx_internal_ext_slice(const float* src, float* dst, int B, int Cs, int cs0, int Cd, int cd0, int Cg, int HW, int accumulate, void* stream);   // dcn_ext.hip
 
 // one deformable group: contiguous NCHW fp32 operands and gradients
 static int backward_one(const float* input, const float* weight, const float* offset, const float* mask, const float* grad_output,

@@ -23,32 +23,10 @@
 #include "../../include/monoflex_hip.h"
 #include "common.h"
 #include "err.h"
+#include "internal.h"
 #include "fill.h"
 #include <algorithm>
 #include <type_traits>
-
-// train_kernels.hip: weight gradient with a dense [M][K] A operand (direct = 1), written as (Cout, Cin, kh, kw)
-int mfx_internal_conv_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int x_pixstride, int Ck,
-                            int kh, int kw, int stride, int pad_h, int pad_w, int Ho, int Wo, int Cout, int ldy,
-                            int dtype, int oihw, int Cin_out, int Cout_out, void* stream, int dil_w,
-                            void* workspace, size_t workspace_bytes, int direct);
-
-int mfx_internal_wgrad_slab_sum(const float* ws, int nslab, int Cout, int Ck, int kh, int kw, float* dw_oihw, void* stream);
-int mfx_internal_colsum_add(const void* x, float* out, long M, int C, int ld, int dtype, void* stream);      // train_kernels.hip: sums ADDED into a zeroed `out`
-
-int g_opt_dcn_bt_fuse_blocks = 170; // option "dcn_bt_fuse_blocks": workgroups per tap group of the fused kernel
-int g_opt_dcn_bt_fly_bias = 1;     // option "dcn_bt_fly_bias": the gcol-free sample kernel also sums grad_bias from the dy rows it loads (0: a separate column-sum pass)
-int g_opt_dcn_bt_gcol_as = 1;      // option "dcn_bt_gcol_as": d(columns) = dy . W^T of the 16-bit layers on the activation-stationary GEMM (gemm_as.hip); 0: the tiled 1x1 kernel
-int g_opt_dcn_bt_fly = 1;          // option "dcn_bt_fly": 64 -> 64 16-bit layers rebuild d(columns) from dy inside both consumers (no [M][9C] matrix in memory)
-long g_cnt_dcn_bt_fly = 0;         // counter "dcn_bt_fly": backward calls that took the gcol-free form
-int g_opt_dcn_bt_fuse_wgrad = 1;   // option "dcn_bt_fuse_wgrad": 64 -> 64 bf16 layers accumulate grad_weight inside the sample kernel (no columns in memory)
-int g_opt_dcn_bt_fuse_min_chunks = 1024; // option "dcn_bt_fuse_min_chunks": fewer 32-pixel chunks than this keep the unfused kernels (tests lower it)
-long g_cnt_dcn_bt_fused = 0;   // counter "dcn_bt_fused": launches of dcn_bwd_sample_wgrad_kernel since process start
-long g_cnt_dcn_bt_tile = 0, g_cnt_dcn_bt_sample = 0, g_cnt_dcn_bt_far = 0;   // counters "dcn_bt_tile" / "dcn_bt_sample" / "dcn_bt_far": launches of
-                               // dcn_bwd_tile_kernel, of dcn_bwd_sample_kernel, of dcn_bwd_far_kernel + dcn_bwd_far_fly_kernel
-int g_opt_dcn_bt_cs = 0;       // option "dcn_bt_cs": channel slice of the tile kernel for C >= 128 (0 = by workgroup count, 64, 128)
-int g_opt_dcn_bt_cs_wgs = 1000; // option "dcn_bt_cs_wgs": below this many 128-channel workgroups the tile kernel takes 64-channel slices
-int g_opt_dcn_bt_dbg = 0;      // option "dcn_bt_dbg": experiment switches of dcn_bwd_tile_kernel (0 in production)
 
 // experiment switches (skip a phase, drop an operand stream: timing probes with WRONG results) exist in probe builds only
 #ifdef MFX_PROBES
@@ -1289,7 +1267,7 @@ static int dcn_backward_v2_impl(const T* x, const float* offmask, const float* w
         // gcol-free form (third generation): 64 -> 64, 16-bit, the shapes the fused sample + weight-gradient kernel takes
         const long nchunks = M / SF_PX;
         const size_t slab_bytes = (size_t)64 * 576 * sizeof(float);
-        if (g_opt_dcn_bt_fly && g_opt_dcn_bt_fuse_wgrad && !g_opt_det && C == 64 && Cout == 64 && W % SF_PX == 0 &&
+        if (g_opt_dcn_bt_fly && g_opt_dcn_bt_fuse_wgrad && !g_opt_deterministic && C == 64 && Cout == 64 && W % SF_PX == 0 &&
             nchunks >= g_opt_dcn_bt_fuse_min_chunks && L.total - L.wg >= 128 * slab_bytes) {
             int nblk = (int)std::min<long>(g_opt_dcn_bt_fuse_blocks, (long)((L.total - L.wg) / slab_bytes));
             const int cpb = (int)((nchunks + nblk - 1) / nblk);
@@ -1371,7 +1349,7 @@ static int dcn_backward_v2_impl(const T* x, const float* offmask, const float* w
         else hipLaunchKernelGGL((dcn_bwd_sample_kernel<T, 16>), sgrid, dim3(256), 0, st, x, offmask, (const T*)gcol, gs, xsplit, d_raw, col);
         ++g_cnt_dcn_bt_sample;
     }
-    if (g_opt_det) {
+    if (g_opt_deterministic) {
         // grad_input through the fixed-point map (the far-corner list's memory: 9 * M * C bytes >= 8 * M * C); see dcn_bwd_dx_fixed_kernel
         unsigned long long* acc = reinterpret_cast<unsigned long long*>(flist);
         const long n = M * C;

@@ -4,6 +4,7 @@
 #include "../../include/monoflex_hip.h"
 #include "common.h"
 #include "err.h"
+#include "internal.h"
 #include "fill.h"
 
 namespace mfx {
@@ -103,8 +104,6 @@ static size_t group_tmp_bytes(int B, int C, int H, int W, int Cout, int kk, int 
               align256((size_t)Cout * 4);
     return o;
 }
-
-extern "C" size_t mfx_dcn_v2_backward_workspace_bytes_(int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw);  // dcn_bwd.hip
 
 extern "C" size_t mfx_dcn_v2_workspace_bytes_g(int B, int C, int H, int W, int Cout, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w,
                                                int dil_h, int dil_w, int deformable_group, int backward);

@@ -28,6 +28,7 @@
 //     unused patch memory, 144 MFMAs per wave, bias + sigmoid, transposition to the owner lanes).
 #include "../../include/monoflex_hip.h"
 #include "err.h"
+#include "internal.h"
 #include "igemm.h"
 
 namespace mfx {
@@ -741,8 +742,6 @@ __global__ __launch_bounds__(256, 2) void dcn_lds_split_kernel(const float* __re
     }
 }
 
-int g_opt_dcn_lds = 1;       // option "dcn_lds": 0 = off, 1 = automatic (64 -> 64 on large 16-bit maps), 2 = wherever the kernel applies
-int g_opt_dcn_lds_rows = 16; // option "dcn_lds_rows": tile rows, 16 | 8 (three workgroups per CU; measured slower: 2.570 vs 2.551 ms per step, profiles/r06_dcn_lds.md)
 
 static bool dcn_lds_shape_ok(const mfx_dcn_desc* d) {
     if (!d->w_pair_f16 || !d->w_frag_f16 || (d->dtype != MFX_BF16 && d->dtype != MFX_F16)) return false;
@@ -755,7 +754,6 @@ static bool dcn_lds_auto(const mfx_dcn_desc* d) {
     if (g_opt_dcn_lds >= 2) return true;
     return d->C == 64 && (long)d->B * d->H * d->W >= 65536;
 }
-extern int g_opt_dcn_fuse_off;
 bool dcn_lds_fuses_offset_conv(const mfx_dcn_desc* d) {
     return g_opt_dcn_fuse_off && d->off_w_frag_f16 && d->off_shift && d->C == 64 && dcn_lds_auto(d);
 }

@@ -25,6 +25,7 @@
 //   * epilogue staged through the (now free) patch memory: 16-byte stores along channels.
 #include "../../include/monoflex_hip.h"
 #include "err.h"
+#include "internal.h"
 #include "igemm.h"
 
 namespace mfx {
@@ -380,13 +381,8 @@ __global__ __launch_bounds__(256, 2) void dcn_patch_kernel(const TX* __restrict_
     }
 }
 
-int g_opt_dcn_patch_fn8 = 1;
-int g_opt_dcn_patch = 1;     // 0 = off, 1 = automatic, 2 = force (FM 4), 3 = force FM 2, 4 = force FM 1, 5-7 = wide margin FM 4/2/1, 8 = padded layout
-
 template <int FN, int FM, int R = 3, int CS = 64, bool PD = false, typename TX = bf16_t, bool OF = false>
 static int launch_dcn_patch_t(const mfx_dcn_desc* d, hipStream_t st);
-
-int g_opt_dcn_fuse_off = 1;  // option "dcn_fuse_off": 1 = the LDS-patch kernel computes the offset/mask conv itself where the caller supplies its weights
 
 template <int FN, int FM, int R = 3, int CS = 64, bool PD = false>
 static int launch_dcn_patch(const mfx_dcn_desc* d, hipStream_t st) {

@@ -20,6 +20,7 @@
 //   * epilogue through a wave-private LDS buffer: 16-byte stores along channels.
 #include "../../include/monoflex_hip.h"
 #include "err.h"
+#include "internal.h"
 #include "igemm.h"
 #include <type_traits>
 
@@ -205,8 +206,6 @@ apply_act_chunk<OE>(v, ep.act, gn);
         __builtin_amdgcn_wave_barrier();
     }
 }
-
-int g_opt_dcn_wave = 1;      // 0 = first-generation kernel only, 1 = automatic, 2.. = force variant
 
 template <typename T, int WN, int FN>
 static int launch_dcn_wave(const mfx_dcn_desc* d, hipStream_t st) {

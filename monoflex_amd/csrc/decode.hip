@@ -410,8 +410,6 @@ __global__ __launch_bounds__(256) void decode_boxes_kernel(const float* hmap, in
 }  // namespace mfx
 using namespace mfx;
 
-int g_opt_topk_merge_z = 16, g_opt_topk_merge_threads = 512;   // options "topk_merge_z" / "topk_merge_threads": workgroups per (class, image) map and their size in the merge
-int g_opt_topk_strips = 8;       // row strips per (class, image) map when a workspace is supplied; 1 = single-workgroup kernel
 
 extern "C" size_t mfx_decode_topk_workspace_bytes(int ncls, int B, int K) {
     return (size_t)B * ncls * 16 * K * 8;                           // up to 16 strips of K (value, index) pairs

@@ -19,6 +19,7 @@
 #include "../../include/monoflex_hip.h"
 #include "common.h"
 #include "err.h"
+#include "internal.h"
 
 namespace mfx {
 

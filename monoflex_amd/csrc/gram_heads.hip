@@ -25,8 +25,6 @@
 #include "fill.h"
 #include <algorithm>
 
-extern long g_cnt_gram;      // dispatch counter (conv_kernels.hip, mfx_get_counter)
-
 namespace mfx {
 
 constexpr int GK = 576, GC = 64, GT = 256;     // patch length (9 taps x 64 channels), input channels, trunk channels per branch
@@ -533,8 +531,8 @@ template <typename T> static int gram_phase(const GD* dp, int phase, hipStream_t
         case 3: {                                                 // row gradients, statistics gradients (caller: all-reduce of `ds` for SyncBN)
             // ONE fill: the caller carved dsum, scal and every branch's d W2 / d b2 out of one arena (d.dsum = its start, scal_bytes its length)
             MFX_HIP_CHECK(mfx::zero_async(d.dsum, (size_t)d.arena_bytes, st));
-            const int rpb = g_opt_det ? std::max(1, d.N) : 16, nco = d.N > 0 ? (d.N + rpb - 1) / rpb : 0;
-            const int rpe = g_opt_det ? std::max(1, d.Ne) : 64, nce = (d.Ne > 0 && d.extra_branch >= 0) ? (d.Ne + rpe - 1) / rpe : 0;
+            const int rpb = g_opt_deterministic ? std::max(1, d.N) : 16, nco = d.N > 0 ? (d.N + rpb - 1) / rpb : 0;
+            const int rpe = g_opt_deterministic ? std::max(1, d.Ne) : 64, nce = (d.Ne > 0 && d.extra_branch >= 0) ? (d.Ne + rpe - 1) / rpe : 0;
             if (nco + nce > 0) hipLaunchKernelGGL(gram_rows_bwd_kernel<T>, dim3(nco + nce, d.nbranch), dim3(256), 0, st, d, rpb, nco, rpe);
             hipLaunchKernelGGL(gram_stats_bwd_kernel, dim3((CH + 255) / 256), dim3(256), 0, st, d);
             break;

@@ -17,13 +17,9 @@
 // Only 3 + 50 fp32 channels per pixel are written.
 #include "../../include/monoflex_hip.h"
 #include "err.h"
+#include "internal.h"
 #include "igemm.h"
 #include <type_traits>
-
-int g_opt_heads_persist = 1;   // option "heads_persist": 1 = one workgroup per resident slot (n > 1: n workgroups), each a contiguous range of (tile, branch)
-                               // units; 0 = one workgroup per tile.  B=8 bf16: 516 -> 503 us (tools/probes/heads_probe.py), bit-identical output
-int g_opt_heads_mfma32 = 0;    // option "heads_mfma32": 1 = the v_mfma_f32_32x32x16 form of the kernel where the caller supplies its packs (mfx_heads_desc.w1_32 / w2_32)
-int g_opt_heads_dbg = 0;       // option "heads_dbg": timing probes of the bf16 kernel (see DBG below); results are wrong -- compiled in with -DMFX_PROBES only
 
 namespace mfx {
 
@@ -633,9 +629,6 @@ template <typename T, bool PL, int DBG = 0> static int launch_heads(const mfx_he
 
 }  // namespace mfx
 using namespace mfx;
-
-int g_opt_heads_planes = 0;    // option "heads_planes": 1 = four k-group planes (no LDS bank conflicts: 48 % -> 11 % of the LDS cycles, LDS-active
-                               // cycles -42 %), 0 = one 144-byte record per pixel.  Same kernel time (555 vs 555 us, A/B in one run): not LDS-bound
 
 extern "C" int mfx_heads_fused(const mfx_heads_desc* d, void* stream) {
     if (!d || !d->x || !d->w1 || !d->scale1 || !d->shift1 || !d->w2 || !d->bias2 || !d->out)

@@ -64,7 +64,7 @@ extern "C" int mfx_focal_loss(const float* logits_nhwc, const float* heat_nchw, 
     const long total = (long)B * H * W * ncls;
     if (total == 0) return MFX_OK;
     unsigned blocks = (unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
-    if (g_opt_det) blocks = 1;                                  // one workgroup: the two sums have a single writer
+    if (g_opt_deterministic) blocks = 1;                                  // one workgroup: the two sums have a single writer
     hipLaunchKernelGGL(focal_loss_kernel, dim3(blocks), dim3(256), 0, st, logits_nhwc, heat_nchw, B, H * W, ncls, alpha, beta, sums2, dlogits_nhwc);
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
@@ -146,7 +146,7 @@ extern "C" int mfx_object_loss(const float* reg_nhwc, int B, int H, int W, int l
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MFX_HIP_CHECK(mfx::zero_async(vals, sizeof(float) * MFX_OBJ_VALUES, st));
     if (N == 0) return MFX_OK;
-    hipLaunchKernelGGL(object_loss_kernel, dim3(g_opt_det ? 1 : N), dim3(64), 0, st, reg_nhwc, B, H, W, ld, ch_off, rows, N, *cfg, vals, G);
+    hipLaunchKernelGGL(object_loss_kernel, dim3(g_opt_deterministic ? 1 : N), dim3(64), 0, st, reg_nhwc, B, H, W, ld, ch_off, rows, N, *cfg, vals, G);
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }
@@ -157,7 +157,7 @@ extern "C" int mfx_object_loss_backward(const float* G, const float* gout_terms,
     if (B < 0 || (B > 0 && (H < 1 || W < 1)) || N < 0 || ch_off < 0 || ch_off + 50 > ld) return mfx_fail(MFX_ERR_ARG, "object_loss_backward: bad sizes");
     if (N == 0) return MFX_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(object_loss_bwd_kernel, dim3(g_opt_det ? 1 : N), dim3(64), 0, st, G, gout_terms, rows, N, B, H, W, dreg_nhwc, ld, ch_off);
+    hipLaunchKernelGGL(object_loss_bwd_kernel, dim3(g_opt_deterministic ? 1 : N), dim3(64), 0, st, G, gout_terms, rows, N, B, H, W, dreg_nhwc, ld, ch_off);
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }

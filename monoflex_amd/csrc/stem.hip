@@ -15,6 +15,7 @@
 #include "../../include/monoflex_hip.h"
 #include "common.h"
 #include "err.h"
+#include "internal.h"
 
 namespace mfx {
 

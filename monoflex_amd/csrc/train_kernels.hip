@@ -5,13 +5,10 @@
 #include "../../include/monoflex_hip.h"
 #include "common.h"
 #include "err.h"
+#include "internal.h"
 #include "fill.h"
 #include "wgrad.h"
 #include <algorithm>
-
-// dispatch counters (conv_kernels.hip, mfx_get_counter): host-side launch counts of each weight-gradient / BN family
-extern long g_cnt_wgrad_patch, g_cnt_wgrad_tr, g_cnt_wgrad_mfma, g_cnt_wgrad_valu, g_cnt_wgrad_reduce;
-extern long g_cnt_bn_fwd_onepass, g_cnt_bn_bwd_onepass, g_cnt_bn_fwd_two, g_cnt_bn_bwd_two;
 
 namespace mfx {
 
@@ -1046,14 +1043,6 @@ __global__ void zero_insert2_kernel(const T* __restrict__ dy, T* __restrict__ up
 }  // namespace mfx
 using namespace mfx;
 
-int g_opt_wgrad_blocks = 600;   // option "wgrad_blocks": target workgroup count of the MFMA weight-gradient kernel (measured, B=8 step:
-                                // 64 -> 146 ms, 150 -> 90, 300 -> 78, 600 -> 73, 2048 -> 75, 8192 -> 81: the tile atomics of every slab cost
-                                // more than the extra workgroups hide)
-int g_opt_wgrad_ws = 1;        // option "wgrad_ws": 0 = always accumulate the tiles with atomics
-int g_opt_wgrad_ws_blocks = 1200;  // option "wgrad_ws_blocks": target workgroup count when partial tiles go to the workspace (step: 1200 -> 58.0 ms, 2400 -> 58.3, 4800 -> 58.6; atomics: 59.6)
-int g_opt_wgrad_min_m = 128;   // option "wgrad_min_m": fewest pixels of a slab of the MFMA weight-gradient kernel.  r06: 1024 left the 1x1 / Root layers of the 24x80 and 12x40 maps with 8-16 slabs (120-240 workgroups of 32 iterations each: 31 us per layer for 4 GFLOP); same-box step 17.50 (1024) / 17.31 (512) / 17.27 (256) / 17.23-17.31 (128) / 17.26 (64) ms
-int g_opt_wgrad_mfma = 1;     // option "wgrad_mfma": 0 = VALU kernel for bf16 too, 1 = 64x64 MFMA tiles, 3 = 128x128 where they fit
-
 // CALL_16 is written once for both 16-bit activation types: T16 = bf16_t or half_t
 #define DISPATCH_T(dtype, CALL_F32, CALL_16) do { if ((dtype) == MFX_F32) { CALL_F32; } else if ((dtype) == MFX_BF16) { using T16 = bf16_t; CALL_16; } \
     else if ((dtype) == MFX_F16) { using T16 = half_t; CALL_16; } else return mfx_fail(MFX_ERR_ARG, "bad dtype"); } while (0)
@@ -1103,7 +1092,7 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw, int B, int 
         g.m_per_block = std::max(std::max(32, g_opt_wgrad_min_m / 32 * 32), (int)(((long)g.M / slabs + 31) / 32 * 32));
         const int nslab = cdivt(g.M, g.m_per_block);
         bool ws_ok = use_ws && (size_t)nslab * ws_slab * sizeof(float) <= workspace_bytes;
-        if (!ws_ok && g_opt_det) { g.m_per_block = (g.M + 31) / 32 * 32; }     // atomics: a single slab per tile adds into zeros exactly once
+        if (!ws_ok && g_opt_deterministic) { g.m_per_block = (g.M + 31) / 32 * 32; }     // atomics: a single slab per tile adds into zeros exactly once
         if (ws_ok) { g.ws = reinterpret_cast<float*>(workspace); g.ws_ld = ws_ld; g.ws_slab = ws_slab; }
         else MFX_HIP_CHECK(mfx::zero_async(dw, dw_bytes, st));
         dim3 grid(cdivt(g.K, bt), cdivt(Cout, bt), cdivt(g.M, g.m_per_block));
@@ -1124,7 +1113,7 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw, int B, int 
         return MFX_OK;
     }
     MFX_HIP_CHECK(mfx::zero_async(dw, dw_bytes, st));
-    if (g_opt_det) g.m_per_block = g.M;                          // one slab: every element of dw receives exactly one add
+    if (g_opt_deterministic) g.m_per_block = g.M;                          // one slab: every element of dw receives exactly one add
     dim3 grid(cdivt(g.K, 64), cdivt(Cout, 64), cdivt(g.M, g.m_per_block));
     ++g_cnt_wgrad_valu;
     DISPATCH_T(dtype, hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (const float*)dy, g, dw),
@@ -1205,9 +1194,6 @@ extern "C" int mfx_pack_conv_weights_batched(const mfx_pack_desc* descs_dev, con
 
 static int bn_rows_per_block(long M, int C, int dtype, int owners);
 
-// library-internal (dcn_bwd_tile.hip): column sums ADDED into `out`, which an earlier kernel of the caller has zeroed
-int mfx_internal_colsum_add(const void* x, float* out, long M, int C, int ld, int dtype, void* stream);
-
 extern "C" int mfx_colsum(const void* x, float* out, long M, int C, int ld, int dtype, void* stream) {
     if (!x || !out) return mfx_fail(MFX_ERR_ARG, "colsum: null pointer");
     MFX_HIP_CHECK(mfx::zero_async(out, (size_t)C * sizeof(float), reinterpret_cast<hipStream_t>(stream)));
@@ -1233,7 +1219,7 @@ int mfx_internal_colsum_add(const void* x, float* out, long M, int C, int ld, in
             return MFX_OK;
         }
     }
-    const int rows = g_opt_det ? (int)M : (M >= (1 << 18) ? 1024 : 128);             // >= ~2 workgroups per CU also on the small head maps
+    const int rows = g_opt_deterministic ? (int)M : (M >= (1 << 18) ? 1024 : 128);             // >= ~2 workgroups per CU also on the small head maps
     dim3 grid(cdivt(M, rows), cdivt(C, 64)), block(64, 4);
     DISPATCH_T(dtype, hipLaunchKernelGGL(colsum_kernel<float>, grid, block, 0, st, (const float*)x, (int)M, C, ld, rows, out),
                       hipLaunchKernelGGL(colsum_kernel<T16>, grid, block, 0, st, (const T16*)x, (int)M, C, ld, rows, out));
@@ -1241,8 +1227,6 @@ int mfx_internal_colsum_add(const void* x, float* out, long M, int C, int ld, in
     return MFX_OK;
 }
 
-int g_opt_bn_apply_blocks = 1024;   // option "bn_apply_blocks": workgroup cap of the two-launch forms' streaming kernels
-int g_opt_bn_blocks = 768;     // option "bn_blocks": target workgroup count of the column reductions (BN statistics / backward sums / bias sums)
 
 // rows per workgroup of the column reductions: every workgroup ends with one global atomic per column, all workgroups on the
 // same 2C addresses (~12 ns each when they collide), so the count is bounded (~3 per CU, 4+ rows in flight per thread hide the
@@ -1251,8 +1235,8 @@ int g_opt_bn_blocks = 768;     // option "bn_blocks": target workgroup count of 
 // launches at most one workgroup per copy, so every copy has a single writer and its adds happen in program order.
 static int bn_rows_per_block(long M, int C, int dtype, int owners) {
     const int E = dtype == MFX_F32 ? 4 : 8, rstep = std::max(1, 256 / (C / E));
-    const int target = g_opt_det ? std::max(1, owners) : (g_opt_bn_blocks > 0 ? g_opt_bn_blocks : 768);
-    if (g_opt_det) {
+    const int target = g_opt_deterministic ? std::max(1, owners) : (g_opt_bn_blocks > 0 ? g_opt_bn_blocks : 768);
+    if (g_opt_deterministic) {
         long rows = (M + target - 1) / target;
         rows = (rows + rstep - 1) / rstep * rstep;
         return (int)std::max<long>(rows, rstep);
@@ -1607,10 +1591,6 @@ __global__ __launch_bounds__(256, 2) void bn_bwd_onepass_kernel(const T* __restr
     bn_release_scratch_bar(sums, counter, bar, ticket, tid, &s_last);
 }
 
-int g_opt_bn_onepass = 3;          // option "bn_onepass": bit 0 = backward, bit 1 = forward in one launch where the map fits (0 = the two-launch forms everywhere)
-int g_opt_bn_onepass_min_chunks = 200000;       // option "bn_onepass_min_chunks": smaller maps keep the two launches (backward)
-int g_opt_bn_onepass_fwd_min_chunks = 900000;   // option "bn_onepass_fwd_min_chunks": the same for the forward
-int g_opt_bn_onepass_grid = 0;     // option "bn_onepass_grid": workgroup cap (0 = by map size, see bn_onepass_plan)
 
 // co-resident workgroups of the one-pass kernels: 2 per CU by their launch bounds; asked of the runtime once per kernel
 template <typename K> static int bn_onepass_capacity(K kernel, size_t smem) {
@@ -1713,7 +1693,7 @@ extern "C" int mfx_bn_train_fwd(const void* x, const void* res, void* y, const f
     const int E = dtype == MFX_F32 ? 4 : 8, ncopy = bn_ncopy(C);
     const int rows = bn_rows_per_block(M, C, dtype, ncopy);
     const size_t smem = (size_t)(256 / (C / E)) * 2 * C * sizeof(float);
-    if (!stats_done && (g_opt_bn_onepass & 2) && !g_opt_det) {          // statistics + element-wise pass in one launch where the map fits the registers of one grid
+    if (!stats_done && (g_opt_bn_onepass & 2) && !g_opt_deterministic) {          // statistics + element-wise pass in one launch where the map fits the registers of one grid
         int r = 1;
         DISPATCH_T(dtype, r = bn_fwd_onepass<float>(x, res, y, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, M, C, act, scratch, mean, rstd, st),
                           r = bn_fwd_onepass<T16>(x, res, y, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, M, C, act, scratch, mean, rstd, st));
@@ -1789,7 +1769,7 @@ extern "C" int mfx_bn_train_bwd(const void* x, const void* a, const void* da, co
     const int E = dtype == MFX_F32 ? 4 : 8, ncopy = bn_ncopy(C);
     const int rows = bn_rows_per_block(M, C, dtype, ncopy);
     const size_t smem = (size_t)(256 / (C / E)) * 2 * C * sizeof(float);
-    if ((g_opt_bn_onepass & 1) && !g_opt_det) {
+    if ((g_opt_bn_onepass & 1) && !g_opt_deterministic) {
         int r = 1;
         DISPATCH_T(dtype, r = bn_bwd_onepass<float>(x, a, da, mean, rstd, gamma, beta, dx, dres, dgamma, dbeta, M, C, act, scratch, st),
                           r = bn_bwd_onepass<T16>(x, a, da, mean, rstd, gamma, beta, dx, dres, dgamma, dbeta, M, C, act, scratch, st));
@@ -1853,7 +1833,7 @@ static int upsample_bwd_impl(const void* x, const float* w, const void* dy, void
     } else {
         if (dw_oihw) return mfx_fail(MFX_ERR_WORKSPACE, "upsample_bwd (parameter-layout gradient): needs the workspace of mfx_upsample_bwd_workspace_bytes");
         MFX_HIP_CHECK(mfx::zero_async(dw, (size_t)4 * f * f * C * sizeof(float), st));
-        ppb = g_opt_det ? nrows : (nrows >= 1024 ? 2 : 1);     // input rows per block: >= ~512 blocks (deterministic: one workgroup)
+        ppb = g_opt_deterministic ? nrows : (nrows >= 1024 ? 2 : 1);     // input rows per block: >= ~512 blocks (deterministic: one workgroup)
     }
     if (total == 0) return MFX_OK;
     const int dw_items = 4 * f * f * (C / E);

@@ -22,8 +22,6 @@
 #include "wgrad.h"
 #include <algorithm>
 
-extern long g_cnt_stem_wgrad;      // dispatch counter (conv_kernels.hip, mfx_get_counter)
-
 namespace mfx {
 
 constexpr int TR_BK = 192, TR_STEP = 32;
@@ -194,8 +192,6 @@ __global__ __launch_bounds__(WO * 192) void conv_wgrad_tr_kernel(const T* __rest
 }  // namespace mfx
 using namespace mfx;
 
-int g_opt_wgrad_tr = 1;          // option "wgrad_tr": 0 = first-generation kernel everywhere
-int g_opt_wgrad_tr_blocks = 512;   // option "wgrad_tr_blocks": target workgroup count (tiles x pixel slabs)
 
 // returns 1 if handled (partial tiles are in g.ws: the caller runs wgrad_reduce_kernel), 0 to fall through
 template <typename T> static int conv_wgrad_tr_t(const void* x, const void* dy, WgradGeom& g, void* workspace, size_t workspace_bytes, int* nslab_out, hipStream_t st);
@@ -444,9 +440,6 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_patch_kernel(const T* __re
 }  // namespace mfx
 using namespace mfx;
 
-int g_opt_wgrad_patch = 1;          // option "wgrad_patch": 0 = off
-int g_opt_wgrad_patch_blocks = 256; // option "wgrad_patch_blocks": target workgroup count
-int g_opt_wgrad_patch_waves = 12;   // option "wgrad_patch_waves": 6 (64 x 96 block per wave) or 12 (64 x 48)
 
 // 3x3 / s1 / p1, Cin % 64 == 0: returns 1 if launched (partials in g.ws, *nslab slabs), 0 to fall through
 template <typename T> static int conv_wgrad_patch_t(const void* x, const void* dy, WgradGeom& g, void* workspace, size_t workspace_bytes, int* nslab_out, hipStream_t st);
@@ -659,8 +652,6 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
 }
 
 }  // namespace mfx
-
-int g_opt_stem_wgrad_blocks = 512;      // option "stem_wgrad_blocks"
 
 extern "C" int mfx_stem_wgrad_bf16(const void* xp, const void* dy, float* dw, int B, int H, int W, int Hp, int Wp, void* workspace,
                                    size_t workspace_bytes, void* stream) {

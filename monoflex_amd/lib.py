@@ -223,11 +223,18 @@ def load():
         raise RuntimeError("libmonoflex_hip.so ABI version mismatch")
     _lib = lib
     # MFX_OPTIONS="name=value,name=value": library tuning switches for this process (mfx_set_option; A/B sweeps of an unmodified bench.py / training script)
-    for kv in filter(None, os.environ.get("MFX_OPTIONS", "").split(",")):
-        k, _, v = kv.partition("=")
-        check(lib.mfx_set_option(k.strip().encode(), int(v)), "MFX_OPTIONS: %s" % kv)
+    set_options(os.environ.get("MFX_OPTIONS", ""), "MFX_OPTIONS")
     check(lib.mfx_commit_options(), "mfx_commit_options")      # mfx_reset_options() now restores the values AFTER the environment's switches
     return lib
+
+
+def set_options(spec, what="set_options"):
+    """Set library tuning switches (mfx_set_option; csrc/options.h lists them): `spec` is "name=value,name=value" or a dict.
+    Raises with the library's message on an unknown name or a value out of range."""
+    lib = load()
+    items = spec.items() if isinstance(spec, dict) else (kv.partition("=")[::2] for kv in filter(None, spec.split(",")))
+    for k, v in items:
+        check(lib.mfx_set_option(k.strip().encode(), int(v)), "%s: %s=%s" % (what, k, v))
 
 
 def f16x2_range_ok(reset=True):

@@ -228,6 +228,90 @@ def test_c_abi_argument_errors_need_no_gpu():
         L.check(lib.mfx_conv2d_nhwc(None, null), "mfx_conv2d_nhwc")
 
 
+CSRC = os.path.join(ROOT, "monoflex_amd", "csrc")
+PROBE_OPTIONS = {"dcn_bt_dbg", "heads_dbg"}            # registered in probe builds (MFX_PROBES) only
+
+
+def _registry():
+    """(switch name -> default, counter names, probe-only switch names) parsed out of the list macros of csrc/options.h."""
+    text = open(os.path.join(CSRC, "options.h")).read()
+
+    def body(macro):                                 # the continuation lines of `#define macro(X) \`
+        m = re.search(r"#define %s\(X\) \\\n((?:.*\\\n)*.*\n)" % macro, text)
+        assert m, macro
+        return m.group(1)
+    option = re.compile(r"^\s*X\((\w+), (-?\d+), (\w+|-?\d+), (\w+|-?\d+), \"", re.M)
+    options = {n: int(d) for n, d, _, _ in option.findall(body("MFX_OPTION_LIST"))}
+    probes = {n for n, _, _, _ in option.findall(body("MFX_PROBE_OPTION_LIST"))}
+    counters = re.findall(r"^\s*X\((\w+), \"", body("MFX_COUNTER_LIST"), re.M)
+    assert len(options) > 50 and len(counters) > 25 and probes == PROBE_OPTIONS, (len(options), len(counters), probes)
+    assert len(set(counters)) == len(counters) and not probes & set(options)
+    return options, counters, probes
+
+
+def _csrc_sources():
+    return {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h"))}
+
+
+def test_option_registry_matches_the_sources():
+    """csrc/options.h is the one list of tuning switches and dispatch counters: every g_opt_<x> / g_cnt_<x> the sources name is listed,
+    every listed name is used by some unit other than the registry (a switch nobody reads, or one that is read but cannot be set, fails
+    here), and nothing but the two registry files defines or declares such a variable."""
+    options, counters, probes = _registry()
+    listed = {"g_opt_" + n for n in set(options) | probes} | {"g_cnt_" + n for n in counters}
+    used = set()
+    for f, src in _csrc_sources().items():
+        names = set(re.findall(r"\bg_(?:opt|cnt)_\w+", src))
+        if f in ("options.h", "options.hip"):
+            continue
+        assert names <= listed, (f, sorted(names - listed))
+        if f.endswith(".hip"):
+            used |= names
+        decl = re.findall(r"^.*\b(?:int|long)\s+g_(?:opt|cnt)_\w+.*$", src, re.M)
+        assert decl == [], (f, decl)
+    assert listed <= used, sorted(listed - used)
+
+
+def test_every_listed_option_and_counter_is_reachable():
+    """Every listed switch takes its own default through mfx_set_option and every listed counter reads 0 in a process that launched
+    nothing; the probe-only switches answer with the probe-build message in a production build."""
+    from monoflex_amd import lib as L
+    lib = L.load()
+    options, counters, probes = _registry()
+    assert options["stem_wgrad_blocks"] == 512
+    try:
+        for n, default in options.items():
+            assert lib.mfx_set_option(n.encode(), default) == 0, (n, lib.mfx_last_error())
+            assert lib.mfx_reset_options() == 0
+        if os.environ.get("MFX_PROBES") != "1":
+            for n in probes:
+                assert lib.mfx_set_option(n.encode(), 0) != 0 and b"probe builds only" in lib.mfx_last_error(), n
+        # value rules that clamp rather than fail (visible through the return code only)
+        assert lib.mfx_set_option(b"dcn_wgrad_m", 1) == 0
+        assert lib.mfx_set_option(b"dcn_bt_fuse_blocks", 0) == 0
+        assert lib.mfx_set_option(b"stem_wgrad_blocks", 0) == 0
+        assert lib.mfx_set_option(b"deterministic", 7) == 0
+    finally:
+        assert lib.mfx_reset_options() == 0
+    for n in counters:
+        assert lib.mfx_get_counter(n.encode()) == 0, n
+
+
+def test_set_options_takes_a_spec_string_or_a_dict():
+    from monoflex_amd import lib as L
+    L.load()
+    try:
+        L.set_options("")
+        L.set_options("halo=0, dcn_lds_rows=8,")
+        L.set_options({"halo": 1, "dcn_wave": "2"})
+        with pytest.raises(RuntimeError, match="unknown option"):
+            L.set_options("halo=1,no_such_option=1")
+        with pytest.raises(RuntimeError, match="topk_merge_z"):
+            L.set_options({"topk_merge_z": 0})
+    finally:
+        L.load().mfx_reset_options()
+
+
 def test_product_code_never_touches_the_oracle():
     """Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may import oracle/; the package itself must not."""
     import re

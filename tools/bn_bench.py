@@ -15,9 +15,7 @@ from monoflex_amd import lib as L
 
 B = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else 8
 if "--opts" in sys.argv:
-    for kv in sys.argv[sys.argv.index("--opts") + 1].split(","):
-        k, v = kv.split("=")
-        L.load().mfx_set_option(k.encode(), int(v))
+    L.set_options(sys.argv[sys.argv.index("--opts") + 1])
 dev = "cuda"
 shapes = [(16, 384, 1280), (32, 192, 640), (64, 96, 320), (128, 48, 160), (256, 24, 80), (512, 12, 40)]
 N = 20

@@ -12,8 +12,7 @@ from monoflex_amd import lib, ops
 
 L = lib.load()
 B0 = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-for kv in filter(None, (sys.argv[2] if len(sys.argv) > 2 else "").split(",")):      # extra library options, k=v,...
-    lib.check(L.mfx_set_option(kv.split("=")[0].encode(), int(kv.split("=")[1])), "opt")
+lib.set_options(sys.argv[2] if len(sys.argv) > 2 else "")      # extra library options, k=v,...
 SHAPES = [(96, 320, 64, 64), (48, 160, 128, 128), (24, 80, 256, 256), (12, 40, 512, 512), (96, 320, 64, 128)]
 N = 20
 

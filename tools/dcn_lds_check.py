@@ -14,7 +14,7 @@ L = lib.load()
 
 
 def opt(k, v):
-    lib.check(L.mfx_set_option(k.encode(), int(v)), "opt")
+    lib.set_options({k: v})
 
 
 ROWS = [8]

@@ -11,9 +11,7 @@ from monoflex_amd import lib, ops
 
 L = lib.load()
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-for kv in filter(None, (sys.argv[2] if len(sys.argv) > 2 else "").split(",")):
-    k, v = kv.split("=")
-    lib.check(L.mfx_set_option(k.encode(), int(v)), "opt")
+lib.set_options(sys.argv[2] if len(sys.argv) > 2 else "")
 SHAPES = [(12, 40, 512, 256), (24, 80, 256, 256), (24, 80, 256, 128), (48, 160, 128, 128), (48, 160, 128, 64), (24, 80, 256, 64)]
 N = 10
 dt = torch.bfloat16

@@ -4,7 +4,7 @@ cat > /tmp/run_bt.py <<PY
 import sys, torch
 sys.path.insert(0, "$R")
 from monoflex_amd import lib as L
-L.check(L.load().mfx_set_option(b"dcn_bt_fly", int(sys.argv[1])), "opt")
+L.set_options({"dcn_bt_fly": sys.argv[1]})
 from tools.train_layer_bench import dominant_kernel_roofline
 r = dominant_kernel_roofline("bf16", 8, torch.device("cuda", 0))
 print(r["avg_launch_ms"])

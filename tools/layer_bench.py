@@ -24,9 +24,7 @@ sys.path.insert(0, ROOT)
 import bench
 
 L = lib.load()
-for kv in filter(None, args.opts.split(",")):
-    k, v = kv.split("=")
-    lib.check(L.mfx_set_option(k.encode(), int(v)), "set_option")
+lib.set_options(args.opts)
 
 model, _, _ = bench.build_model(args.dtype, torch.device("cuda", 0))
 B = args.batch

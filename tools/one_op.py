@@ -28,9 +28,7 @@ a = ap.parse_args()
 
 from monoflex_amd import autograd as AG, lib, ops
 L = lib.load()
-for kv in filter(None, a.opts.split(",")):
-    k, v = kv.split("=")
-    lib.check(L.mfx_set_option(k.encode(), int(v)), "opt")
+lib.set_options(a.opts)
 dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
 torch.manual_seed(0)
 

@@ -12,7 +12,7 @@ from monoflex_amd import lib, ops
 
 L = lib.load()
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-OPTS = [kv.split("=") for kv in filter(None, (sys.argv[2] if len(sys.argv) > 2 else "").split(","))]
+OPTS = sys.argv[2] if len(sys.argv) > 2 else ""
 dt = torch.bfloat16
 LAYERS = [("level2 project", 96, 320, [32], 64, 0), ("level2 root", 96, 320, [64, 64], 64, 1), ("level3 project", 48, 160, [64], 128, 0),
           ("level3 tree1 root", 48, 160, [128, 128], 128, 1), ("level3 root", 48, 160, [128, 128, 64, 128], 128, 1), ("level4 project", 24, 80, [128], 256, 0),
@@ -59,8 +59,7 @@ for (name, H, W, chans, Co, act) in LAYERS:
     for pf in (0, 2):
         lib.check(L.mfx_reset_options(), "reset")
         if pf:
-            for k_, v_ in OPTS:
-                lib.check(L.mfx_set_option(k_.encode(), int(v_)), "opt")
+            lib.set_options(OPTS)
         y = fn().clone()
         res[pf] = (timed(fn), y)
     floor = (B * H * W * (K + Co) * 2 + Co * K * 2) / 6.3e12 * 1e6

@@ -21,8 +21,7 @@ N = 10
 
 def opt(**kw):
     lib.check(L.mfx_reset_options(), "reset")
-    for k, v in kw.items():
-        lib.check(L.mfx_set_option(k.encode(), int(v)), "opt")
+    lib.set_options(kw)
 
 
 def timed(fn):

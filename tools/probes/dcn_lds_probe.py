@@ -12,7 +12,7 @@ import torch
 from monoflex_amd import lib, ops
 
 L = lib.load()
-lib.check(L.mfx_set_option(b"dcn_lds_rows", int(os.environ.get("DCN_LDS_ROWS", "8"))), "opt")
+lib.set_options({"dcn_lds_rows": os.environ.get("DCN_LDS_ROWS", "8")})
 mode = sys.argv[1] if len(sys.argv) > 1 else "module"
 B, H, W, C = [int(v) for v in sys.argv[2:6]] if len(sys.argv) > 5 else (8, 96, 320, 64)
 dt = torch.bfloat16

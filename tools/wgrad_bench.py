@@ -17,9 +17,7 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--only", default="", help="substring of the shape name")
 a = ap.parse_args()
 lib = L.load()
-for kv in filter(None, a.opts.split(",")):
-    k, v = kv.split("=")
-    L.check(lib.mfx_set_option(k.encode(), int(v)), "opt")
+L.set_options(a.opts)
 SHAPES = [  # name, B, H, W, Cin, Cout, k, stride
     ("heads 64->256 @96x320", 8, 96, 320, 64, 256, 3, 1), ("level2 64->64 @96x320", 8, 96, 320, 64, 64, 3, 1),
     ("level3 128->128 @48x160", 8, 48, 160, 128, 128, 3, 1), ("level4 256->256 @24x80", 8, 24, 80, 256, 256, 3, 1),
