@@ -516,7 +516,8 @@ int mfx_focal_loss(const float* logits_nhwc, const float* heat_nchw, int B, int 
  *   reg   fp32 NHWC map, pixel stride `ld`, the 50 regression channels at [ch_off, ch_off + 50) of every pixel
  *   vals  fp32 [MFX_OBJ_VALUES] (overwritten): [0, MFX_OBJ_TERMS) the weighted loss terms bbox, depth, offset, trunc_offset, orien,
  *         dims, corner, keypoint, keypoint_depth, weighted_avg_depth; then the logged means (2D_IoU, depth_loss, keypoint_depth_loss,
- *         depth / center / 02 / 13 / lower / hard / soft / mean MAE)
+ *         depth / center / 02 / 13 / lower / hard / soft / mean MAE, and in slot 21 the 3D_IoU: the mean over the valid rows of the rotated
+ *         3D box IoU of the decoded predicted box with its target box, mfx_box3d_iou_pairs' arithmetic); slots 22, 23 are spare (zero)
  *   G     fp32 [N][MFX_OBJ_TERMS][64] (overwritten): d(term)/d(channel) at the object's pixel
  * mfx_object_loss_backward ADDS sum_t gout[t] * G[n][t][c] into dreg (same geometry as reg; the caller zero-fills it): objects
  * sharing a centre pixel accumulate, as the gather's backward does.
@@ -541,6 +542,17 @@ int mfx_object_loss(const float* reg_nhwc, int B, int H, int W, int ld, int ch_o
                     const mfx_object_loss_cfg* cfg, float* vals, float* G, void* stream);
 int mfx_object_loss_backward(const float* G, const float* gout_terms, const float* rows, int N, int B, int H, int W,
                              float* dreg_nhwc, int ld, int ch_off, void* stream);
+
+/* Rotated 3D box IoU of N matched box pairs (csrc/box3d_iou.hip; reference get_iou_3d, model/layers/iou_loss.py:99-136, the logged
+ * `3D_IoU` of model/head/detector_loss.py:333,436 -- there a host loop over shapely polygons).  Upright boxes rotated about Y:
+ * iou[n] = bottom overlap * height overlap / (area_a * h_a + area_b * h_b - that), the bottom overlap being the intersection area of the two
+ * x-z rectangles, the height overlap that of the intervals [-(y + h/2), -(y - h/2)].  fp32; both rectangles are moved to box b's centre first.
+ *   form 0: boxes_a / boxes_b fp32 [N][7] rows (x, y, z, l, h, w, ry), y = the box CENTRE (what encode_box3d builds its corners around)
+ *   form 1: fp32 [N][8][3] corner tables in encode_box3d order (anno_encoder.py:88-122), what get_iou_3d receives: heights = mean y of corners
+ *           0..3 and 4..7, bottom polygon = corners 0..3 (x, z), assumed convex
+ *   iou   : fp32 [N] (overwritten).  A pair whose union is <= 0 or not finite gives 0, never NaN.
+ * One lane per pair, one launch on `stream`, nothing allocated, no synchronisation; N == 0 returns MFX_OK without a launch. */
+int mfx_box3d_iou_pairs(const float* boxes_a, const float* boxes_b, int N, int form, float* iou, void* stream);
 
 /* Regression branches of the training step evaluated at the object centres only (csrc/head_sparse.hip; reference
  * model/head/detector_predictor.py:125-169 + the gather of model/layers/utils.py:120-145).  Per branch i: y[i] = the dense trunk

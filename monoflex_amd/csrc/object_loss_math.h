@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "../../include/monoflex_hip.h"
+#include "box3d_iou_math.h"
 
 #ifndef MFX_HD
 #ifdef __HIPCC__
@@ -28,10 +29,11 @@ constexpr int ROW = MFX_OBJ_ROW, NTERM = MFX_OBJ_TERMS, NVAL = MFX_OBJ_VALUES, N
 // target row fields (float32 each; written by Loss_Computation.pack_objects)
 enum { R_VALID = 0, R_CLS, R_CX, R_CY, R_BOX = 4, R_KP = 8, R_KDM = 38, R_DIMS = 41, R_DEPTH = 44, R_ROTY, R_ORI = 46, R_OFF = 54,
        R_TRUNC = 56, R_B, R_CAL = 58, R_PAD = 64, R_FU_RANK = 66 };
-// loss terms (the reference's names), then the logged values
+// loss terms (the reference's names), then the logged values (V_IOU3D = slot 21: the first of the three spare slots)
 enum { T_BBOX = 0, T_DEPTH, T_OFFSET, T_TRUNC_OFFSET, T_ORIEN, T_DIMS, T_CORNER, T_KEYPOINT, T_KEYPOINT_DEPTH, T_SOFT_DEPTH,
        V_IOU2D = 10, V_REAL_DEPTH, V_VALID_KD, V_DEPTH_MAE, V_CENTER_MAE, V_02_MAE, V_13_MAE, V_LOWER_MAE, V_HARD_MAE, V_SOFT_MAE,
-       V_MEAN_MAE };
+       V_MEAN_MAE, V_IOU3D };
+static_assert(V_IOU3D == 21 && V_IOU3D < NVAL, "the logged 3D IoU is value slot 21");
 enum { N_V = 0, N_V2D, N_V_INSIDE, N_TRUNC, N_KMASK, N_KD_VALID, N_KD_INVALID, N_ORI };
 enum { C_2D = 0, C_OFF3D, C_CORNER, C_CORNER_UNC, C_DIM, C_ORI_CLS, C_ORI_OFF, C_DEPTH, C_DEPTH_UNC };
 
@@ -223,6 +225,10 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
             l = l + dabs(a.x - b.x) + dabs(a.y - b.y) + dabs(a.z - b.z);
         }
         out[T_CORNER] = l * (c.w[T_CORNER] * inv_v / 8.f);
+        // the logged 3D IoU of the same two boxes (detector_loss.py:333,436 get_iou_3d): values only, no tangent
+        const float pl[3] = {p_loc.x.v, p_loc.y.v, p_loc.z.v}, pd[3] = {p_dims[0].v, p_dims[1].v, p_dims[2].v};
+        const float tl[3] = {t_loc.x.v, t_loc.y.v, t_loc.z.v};
+        out[V_IOU3D] = K(biou::iou_parts(pl, pd, pc.v, ps.v, tl, t + R_DIMS, tc.v, ts.v) * inv_v);
     }
     // ---- keypoints (visible ones) ----------------------------------------------------------------------------------------------
     {

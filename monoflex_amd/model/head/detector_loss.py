@@ -20,6 +20,7 @@ import math
 import torch
 import torch.nn.functional as F
 
+from ..layers.iou_loss import get_iou_3d
 from ..layers.utils import Converter_key2channel
 
 PI = math.pi
@@ -378,7 +379,7 @@ class Loss_Computation:
                           'weighted_avg_depth_loss': t[9]})
         with torch.no_grad():
             lg = logged.unbind(0)
-            logs = {'2D_IoU': lg[0], '3D_IoU': lg[0] * 0, 'depth_loss': lg[1], 'keypoint_depth_loss': lg[2]}
+            logs = {'2D_IoU': lg[0], '3D_IoU': lg[11], 'depth_loss': lg[1], 'keypoint_depth_loss': lg[2]}
             for key, val in loss_dict.items():
                 if key not in logs:
                     logs[key] = val.detach()
@@ -469,7 +470,7 @@ class Loss_Computation:
             kMAE = (kd - t_kd).abs() / t_depth_safe.unsqueeze(-1)
             cMAE = torch.cat((depth_MAE.unsqueeze(1), kMAE), dim=1)
             hard = cMAE.gather(1, comb_unc.argmin(dim=1, keepdim=True)).squeeze(1)
-            logs = {'2D_IoU': _wmean(iou2d, v2), '3D_IoU': torch.zeros((), device=dev),
+            logs = {'2D_IoU': _wmean(iou2d, v2), '3D_IoU': _wmean(get_iou_3d(P['corners_3D'], T['corners_3D']), v),
                     'depth_loss': real_depth_loss, 'keypoint_depth_loss': log_valid_kd}
             for key, val in loss_dict.items():
                 if key not in logs:

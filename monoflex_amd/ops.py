@@ -854,3 +854,18 @@ def ext_dcn_v2_psroi_pooling_backward(grad_output, input, rois, offset, output_c
                                                        pooled_size, part_size, sample_per_part, trans_std, _stream()),
             "mfx_dcn_v2_psroi_pooling_backward")
     return gi, goff
+
+
+@on_tensor_device
+def box3d_iou(a, b):
+    """Rotated 3D box IoU of N matched pairs (mfx_box3d_iou_pairs; reference get_iou_3d, model/layers/iou_loss.py:99-136) -> (N,) fp32.
+    `a`, `b`: both (N, 7) rows (x, y, z, l, h, w, ry) with y the box centre, or both (N, 8, 3) corner tables in encode_box3d order.
+    One launch on the current stream, no host synchronisation."""
+    _need_cuda(a, b)
+    if a.shape != b.shape or not ((a.dim() == 2 and a.shape[1] == 7) or (a.dim() == 3 and tuple(a.shape[1:]) == (8, 3))):
+        raise RuntimeError("box3d_iou: both operands must be (N, 7) box rows or (N, 8, 3) corner tables, got %s and %s"
+                           % (tuple(a.shape), tuple(b.shape)))
+    x, y = a.detach().float().contiguous(), b.detach().float().contiguous()
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    L.check(L.load().mfx_box3d_iou_pairs(_ptr(x), _ptr(y), x.shape[0], 0 if x.dim() == 2 else 1, _ptr(out), _stream()), "mfx_box3d_iou_pairs")
+    return out
