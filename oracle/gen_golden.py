@@ -303,6 +303,41 @@ def run_decode_cases():
     np.savez_compressed(os.path.join(GOLD, "decode_only.npz"), **out)
 
 
+STRUCTURED = dict(map_seed=21, list_seed=22, K=50, score_ranges=[(0.02, 0.245), (0.05, 0.23), (0.02, 0.22), (0.02, 0.235)])
+
+
+def run_decode_structured():
+    """Reference PostProcessor on the structured head maps of tests/decode_cases.py (every decode branch taken: keypoint depths below the
+    clamp, both clamps of the direct depth and of sigma, all four clip sides, every orientation bin, both wraps), four images with their own
+    pad / size / calibration, one at a time, under every `output_depth`.  The class heat map holds isolated peaks with distinct scores, so
+    the order of the rows does not hang on torch.topk's treatment of equals; the score ranges leave 15-30 of an image's 50 slots above the
+    threshold.  Stored: the seeds and the result rows (all 14 columns under 'soft', columns 9-13 under the other modes)."""
+    from tests import decode_cases as C
+    cfg, model = build_reference(C.W, C.H)
+    post = model.heads.post_processor
+    assert post.max_detection == STRUCTURED["K"] and post.det_threshold == C.THRESHOLD
+    images = (0, 1, 2, 3)
+    maps = C.structured_maps(STRUCTURED["map_seed"], images)
+    scores, index = C.peak_lists(STRUCTURED["list_seed"], len(images), STRUCTURED["K"], STRUCTURED["score_ranges"])
+    base = S.synthetic_target(C.W, C.H)
+    out = {k: np.array(v) for k, v in STRUCTURED.items()}
+    out["images"] = np.array(images)
+    for b, i in enumerate(images):
+        tgt = dict(base, P=C.image_P(i), size=tuple(C.IMAGES[i]["size"]), pad_size=torch.tensor(C.IMAGES[i]["pad"], dtype=torch.int64))
+        cls = torch.from_numpy(C.peak_heat(scores, index, b))[None]
+        reg = torch.from_numpy(maps["hmap"][b, :, :, maps["reg_off"]:maps["reg_off"] + 50]).permute(2, 0, 1)[None].contiguous()
+        for mode in ["soft"] + DEPTH_MODES:
+            post.output_depth = mode
+            r, _, _ = post({"cls": cls.clone(), "reg": reg.clone()}, [reference_target(tgt)], test=True)
+            # (the depth mode enters a row through X, Y, Z, ry and the score only: columns 9-13; test_decode_ref_cpu.py checks the rest is equal)
+            assert mode == "soft" or np.array_equal(r.numpy()[:, :9], out["img%d_result_soft" % b][:, :9])
+            out["img%d_result_%s" % (b, mode)] = r.numpy() if mode == "soft" else r.numpy()[:, 9:]
+        post.output_depth = "soft"
+        print("decode_structured image", i, "rows", tuple(r.shape))
+    out["meta"] = np.array(repr(dict(case="decode_structured", torch=torch.__version__, inputs="tests/decode_cases.py structured_maps / peak_lists")))
+    np.savez_compressed(os.path.join(GOLD, "decode_structured.npz"), **out)
+
+
 def reference_train_target(tgt):
     from monoflex_amd.structures.params_3d import TRAIN_FIELDS
     t = reference_target(tgt)
@@ -703,6 +738,8 @@ if __name__ == "__main__":
         run_case("e2e_small", 32, 16, seeds=(1000, 1001), cls_bias=-1.0, store_full=True)
     if "decode" in which:
         run_decode_cases()
+    if "decode_structured" in which:
+        run_decode_structured()
     if "full" in which:
         # BASELINE configs[0]'s four seeded images (1000 ..; a seed whose top-51 scores hold a near-tie is skipped) and one image at the
         # reference's default class bias -log(1/0.01 - 1) (detector_predictor.py:43: nothing passes the 0.2 threshold there -- the zero-detection path at full size)
