@@ -14,6 +14,7 @@
 #include "err.h"
 #include "internal.h"
 #include "fill.h"
+#include "dcn_sample_math.h"
 #include <type_traits>
 
 namespace mfx {
@@ -31,26 +32,24 @@ template <> __device__ __forceinline__ f32x4 ld4<bf16_t>(const bf16_t* p) {
 
 struct BwdGeom { int B, H, W, Cp, lgC, Ho, Wo, kh, kw, kk, stride, pad, dil, M, K, Kp, Coutp, stride_w, pad_w, dil_w; };      // stride / pad / dil: rows; *_w: columns
 
-struct TapGeo { int off[4]; float w[4]; float lh, lw, hh, hw; bool inside; bool cv[4]; };
+struct TapGeo { int off[4]; float w[4]; dcns::CoordWeights d; bool inside; bool cv[4]; };
 
-// geometry of one (pixel, tap) sample -- same rules as the forward sampler (dcn_v2_im2col_cuda.cu:25-54,178-189)
+// geometry of one (pixel, tap) sample: dcn_sample_math.h plus the (clamped) pixel index of each corner
 __device__ __forceinline__ TapGeo tap_geometry(const BwdGeom& g, const float* om_row, int b, int oh, int ow, int tap) {
     TapGeo t;
-    const int th = tap / g.kw, tw = tap - th * g.kw;
-    const float h = (float)(oh * g.stride - g.pad + th * g.dil) + om_row[2 * tap];
-    const float w = (float)(ow * g.stride_w - g.pad_w + tw * g.dil_w) + om_row[2 * tap + 1];
-    t.inside = h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W;
-    const float hf = floorf(h), wf = floorf(w);
-    const int h0 = (int)hf, w0 = (int)wf, h1 = h0 + 1, w1 = w0 + 1;
-    t.lh = h - hf; t.lw = w - wf; t.hh = 1.f - t.lh; t.hw = 1.f - t.lw;
-    const bool t0 = t.inside && h0 >= 0, t1 = t.inside && h1 <= g.H - 1, l0 = w0 >= 0, l1 = w1 <= g.W - 1;
-    const int ch0 = min(max(h0, 0), g.H - 1), ch1 = min(max(h1, 0), g.H - 1);
-    const int cw0 = min(max(w0, 0), g.W - 1), cw1 = min(max(w1, 0), g.W - 1);
+    const dcns::Tap tp = dcns::tap_of(tap, g.kw);
+    const float h = dcns::pos(oh, g.stride, g.pad, tp.th, g.dil, om_row[dcns::off_h(tap)]);
+    const float w = dcns::pos(ow, g.stride_w, g.pad_w, tp.tw, g.dil_w, om_row[dcns::off_w(tap)]);
+    t.inside = dcns::inside(h, w, g.H, g.W);
+    const dcns::Sample s = dcns::sample<dcns::kClampLo, dcns::kClampHiWide>(h, w);      // any map below 4 GB: see dcn_sample_math.h
+    t.d = dcns::coord_weights(s);
     const int pix0 = b * g.H * g.W;
-    t.off[0] = pix0 + ch0 * g.W + cw0; t.cv[0] = t0 && l0; t.w[0] = t.hh * t.hw;
-    t.off[1] = pix0 + ch0 * g.W + cw1; t.cv[1] = t0 && l1; t.w[1] = t.hh * t.lw;
-    t.off[2] = pix0 + ch1 * g.W + cw0; t.cv[2] = t1 && l0; t.w[2] = t.lh * t.hw;
-    t.off[3] = pix0 + ch1 * g.W + cw1; t.cv[3] = t1 && l1; t.w[3] = t.lh * t.lw;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        t.off[q] = pix0 + dcns::clamp_idx(dcns::corner_h(s, q), g.H) * g.W + dcns::clamp_idx(dcns::corner_w(s, q), g.W);
+        t.cv[q] = dcns::corner_valid(s, t.inside, q, g.H, g.W);
+        t.w[q] = dcns::corner_weight(s, q);
+    }
     return t;
 }
 
@@ -70,8 +69,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_kernel(const T* x, const f
     for (long pair = wave_id; pair < (long)g.M * g.kk; pair += nwaves) {
         const int m = (int)(pair / g.kk), tap = (int)(pair - (long)m * g.kk);
         const int hw = g.Ho * g.Wo, b = m / hw, rem = m - b * hw, oh = rem / g.Wo, ow = rem - oh * g.Wo;
-        const float* om_row = om + (size_t)m * 32;
-        const float mask = om_row[18 + tap];
+        const float* om_row = om + (size_t)m * dcns::kRow;
+        const float mask = om_row[dcns::mask_at(tap)];
         const TapGeo t = tap_geometry(g, om_row, b, oh, ow, tap);
         float gm = 0.f, gh = 0.f, gw = 0.f;
         if (t.inside) {
@@ -81,9 +80,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_kernel(const T* x, const f
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = t.cv[q] ? ElemTraits<T>::load(x + (size_t)t.off[q] * g.Cp + c) : 0.f;
                 gm += gc * (t.w[0] * v[0] + t.w[1] * v[1] + t.w[2] * v[2] + t.w[3] * v[3]);
-                // dmcn_get_coordinate_weight (dcn_v2_im2col_cuda.cu:82-122)
-                gh += (-t.hw * v[0] - t.lw * v[1] + t.hw * v[2] + t.lw * v[3]) * gc * mask;
-                gw += (-t.hh * v[0] + t.hh * v[1] - t.lh * v[2] + t.lh * v[3]) * gc * mask;
+                gh += (t.d.ch[0] * v[0] + t.d.ch[1] * v[1] + t.d.ch[2] * v[2] + t.d.ch[3] * v[3]) * gc * mask;
+                gw += (t.d.cw[0] * v[0] + t.d.cw[1] * v[1] + t.d.cw[2] * v[2] + t.d.cw[3] * v[3]) * gc * mask;
                 const float top = gc * mask;                  // col2im (dcn_v2_im2col_cuda.cu:197-254)
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
@@ -92,8 +90,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_kernel(const T* x, const f
         }
         gm = wave_sum(gm); gh = wave_sum(gh); gw = wave_sum(gw);
         if (lane == 0) {
-            float* o = gom + (size_t)m * 32;
-            o[2 * tap] = gh; o[2 * tap + 1] = gw; o[18 + tap] = gm;
+            float* o = gom + (size_t)m * dcns::kRow;
+            o[dcns::off_h(tap)] = gh; o[dcns::off_w(tap)] = gw; o[dcns::mask_at(tap)] = gm;
         }
     }
 }
@@ -128,9 +126,9 @@ __global__ __launch_bounds__(256) void dcn_bwd_wgrad_kernel(const T* x, const fl
             if (k < g.K) {                                   // Cp >= 16 -> the 4 k's share one tap
                 const int tap = k >> g.lgC, c = k & (g.Cp - 1);
                 const int b = m / hw, rem = m - b * hw, oh = rem / g.Wo, ow = rem - oh * g.Wo;
-                const float* om_row = om + (size_t)m * 32;
+                const float* om_row = om + (size_t)m * dcns::kRow;
                 const TapGeo t = tap_geometry(g, om_row, b, oh, ow, tap);
-                const float mask = om_row[18 + tap];
+                const float mask = om_row[dcns::mask_at(tap)];
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     if (t.cv[q]) {

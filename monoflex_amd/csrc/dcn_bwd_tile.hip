@@ -25,6 +25,7 @@
 #include "err.h"
 #include "internal.h"
 #include "fill.h"
+#include "dcn_sample_math.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -61,22 +62,12 @@ template <typename T> __device__ __forceinline__ void raw_put(float* graw, int r
     if (raw16) ElemTraits<T>::store(reinterpret_cast<T*>(graw) + idx, v); else graw[idx] = v;
 }
 
-struct SampGeo { int h0, w0; float lh, lw, mask; int inside; };
-
-// sampling geometry of (pixel (my,mx), tap): same rules as the forward sampler (dcn_v2_im2col_cuda.cu:25-54,178-189)
-__device__ __forceinline__ SampGeo samp_geo(const BtGeom& g, const float* __restrict__ om_row, int my, int mx, int tap) {
-    SampGeo s;
-    const int th = (tap * 11) >> 5, tw = tap - th * 3;        // tap / 3 for 0..8
-    const float h = (float)(my - 1 + th) + om_row[2 * tap];
-    const float w = (float)(mx - 1 + tw) + om_row[2 * tap + 1];
-    s.inside = (h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W) ? 1 : 0;
-    const float hf = floorf(h), wf = floorf(w);
-    s.lh = h - hf; s.lw = w - wf;
-    // clamp before the int conversion: a wild (or NaN) offset must not overflow; such a sample is not `inside` anyway
-    s.h0 = (int)fminf(fmaxf(hf, -4.f), 32000.f);
-    s.w0 = (int)fminf(fmaxf(wf, -4.f), 32000.f);
-    s.mask = om_row[18 + tap];
-    return s;
+// geometry of sample (pixel (my, mx), tap) of a 3x3 / stride 1 / pad 1 layer from its raw offsets (dcn_sample_math.h)
+struct SampGeo { bool inside; dcns::Sample s; };
+__device__ __forceinline__ SampGeo samp_geo(const BtGeom& g, int my, int mx, int tap, float dh, float dw) {
+    const dcns::Tap t = dcns::tap3x3(tap);
+    const float h = dcns::pos3x3(my, t.th, dh), w = dcns::pos3x3(mx, t.tw, dw);
+    return SampGeo{dcns::inside(h, w, g.H, g.W), dcns::sample(h, w)};
 }
 
 // two transposed 8-byte LDS reads (ds_read_b64_tr_b16: the 16-bit elements of a 16-lane group's rows come back transposed), at `a` and `a + 512`
@@ -224,18 +215,16 @@ __global__ __launch_bounds__(256) void dcn_bwd_tile_kernel(const float* __restri
         }
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            const int th = tap / 3, tw = tap - th * 3;
-            const float h = (float)(my - 1 + th) + o[2 * tap], w = (float)(mx - 1 + tw) + o[2 * tap + 1];
-            const float mask = o[18 + tap];
-            if (!(h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W) || mask == 0.f) continue;
-            const float hf = floorf(h), wf = floorf(w);
-            const float lh = h - hf, lw = w - wf, hh = 1.f - lh, hw = 1.f - lw;
-            const int h0 = (int)hf, w0 = (int)wf;                             // inside => -1 <= h0 < H: no overflow
+            const dcns::Tap t = dcns::tap3x3(tap);
+            const float h = dcns::pos3x3(my, t.th, o[dcns::off_h(tap)]), w = dcns::pos3x3(mx, t.tw, o[dcns::off_w(tap)]);
+            const float mask = o[dcns::mask_at(tap)];
+            if (!dcns::inside(h, w, g.H, g.W) || mask == 0.f) continue;
+            const dcns::Sample s = dcns::sample_inside(h, w);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int hc = h0 + (q >> 1), wc = w0 + (q & 1);
-                const float wq = ((q >> 1) ? lh : hh) * ((q & 1) ? lw : hw) * mask;
-                if (hc < 0 || hc >= g.H || wc < 0 || wc >= g.W || wq == 0.f) continue;
+                const int hc = dcns::corner_h(s, q), wc = dcns::corner_w(s, q);
+                const float wq = dcns::corner_weight(s, q) * mask;
+                if (!dcns::in_map(hc, wc, g.H, g.W) || wq == 0.f) continue;
                 const int ly = hc - ty0, lx = wc - tx0;
                 if (ly >= 0 && ly < BT_TH && lx >= 0 && lx < BT_TW) {
                     const int p = ly * BT_TW + lx;
@@ -260,8 +249,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_tile_kernel(const float* __restri
                 const uint2 en = fstage[i];
                 const int q = (int)(en.x >> 28), emy = (int)((en.x >> 16) & 0xfff), emx = (int)((en.x >> 4) & 0xfff), etap = (int)(en.x & 15);
                 const size_t m = (size_t)(mb + (long)emy * g.W + emx);
-                const SampGeo sg = samp_geo(g, om + m * 32, emy, emx, etap);
-                far_entry(fbase + i, m, etap, sg.h0 + (q >> 1), sg.w0 + (q & 1), en.y);
+                const SampGeo sg = samp_geo(g, emy, emx, etap, om[m * dcns::kRow + dcns::off_h(etap)], om[m * dcns::kRow + dcns::off_w(etap)]);
+                far_entry(fbase + i, m, etap, dcns::corner_h(sg.s, q), dcns::corner_w(sg.s, q), en.y);
             }
         }
     }
@@ -371,17 +360,18 @@ __global__ __launch_bounds__(256) void dcn_bwd_dx_fixed_kernel(const float* __re
         const long m = s / 9;
         const int tap = (int)(s - m * 9);
         const int b = (int)(m / HW), rem = (int)(m - (long)b * HW), my = rem / g.W, mx = rem - my * g.W;
-        const SampGeo sg = samp_geo(g, om + m * 32, my, mx, tap);
-        if (!sg.inside || sg.mask == 0.f) continue;
-        const float hh = 1.f - sg.lh, hw = 1.f - sg.lw;
+        const float* r = om + m * dcns::kRow;
+        const float mask = r[dcns::mask_at(tap)];
+        const SampGeo sg = samp_geo(g, my, mx, tap, r[dcns::off_h(tap)], r[dcns::off_w(tap)]);
+        if (!sg.inside || mask == 0.f) continue;
         for (int c = cl * 8; c < g.C; c += 64) {
             float gq[8];
             bt_load8<T>(gcol + m * g.Kp + tap * g.C + c, gq);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int hc = sg.h0 + (q >> 1), wc = sg.w0 + (q & 1);
-                const float wq = ((q >> 1) ? sg.lh : hh) * ((q & 1) ? sg.lw : hw) * sg.mask;
-                if (hc < 0 || hc >= g.H || wc < 0 || wc >= g.W || wq == 0.f) continue;
+                const int hc = dcns::corner_h(sg.s, q), wc = dcns::corner_w(sg.s, q);
+                const float wq = dcns::corner_weight(sg.s, q) * mask;
+                if (!dcns::in_map(hc, wc, g.H, g.W) || wq == 0.f) continue;
                 unsigned long long* ap = acc + ((size_t)b * HW + (size_t)hc * g.W + wc) * g.C + c;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -444,8 +434,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_kernel(const T* __restrict
         Pre p = {0.f, 0.f, 0.f};
         if (j < nsamp) {
             const int px = j / 9, tap = j - px * 9;
-            const float* r = om + (mrow + x_begin + px) * 32;
-            p.oh = r[2 * tap]; p.ow = r[2 * tap + 1]; p.mk = r[18 + tap];
+            const float* r = om + (mrow + x_begin + px) * dcns::kRow;
+            p.oh = r[dcns::off_h(tap)]; p.ow = r[dcns::off_w(tap)]; p.mk = r[dcns::mask_at(tap)];
         }
         return p;
     };
@@ -455,12 +445,10 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_kernel(const T* __restrict
         q.ok = j < nsamp;
         const int px = j / 9, mx = x_begin + px;
         q.tap = j - px * 9;
-        const int th = (q.tap * 11) >> 5, tw = q.tap - th * 3;
-        const float h = (float)(my - 1 + th) + p.oh, w = (float)(mx - 1 + tw) + p.ow;
-        q.inside = q.ok && h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W;
-        const float hf = floorf(h), wf = floorf(w);
-        q.lh = h - hf; q.lw = w - wf; q.mask = p.mk;
-        q.h0 = (int)fminf(fmaxf(hf, -4.f), 32000.f); q.w0 = (int)fminf(fmaxf(wf, -4.f), 32000.f);
+        const SampGeo sg = samp_geo(g, my, mx, q.tap, p.oh, p.ow);
+        q.inside = q.ok && sg.inside;
+        q.lh = sg.s.lh; q.lw = sg.s.lw; q.mask = p.mk;
+        q.h0 = sg.s.h0; q.w0 = sg.s.w0;
         q.m = mrow + mx;
         return q;
     };
@@ -473,7 +461,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_kernel(const T* __restrict
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const int hc = q.h0 + (c >> 1), wc = q.w0 + (c & 1);
-                if (hc >= 0 && hc < g.H && wc >= 0 && wc < g.W) r.v[c].load(xb + ((size_t)hc * g.W + wc) * g.C + c0);
+                if (dcns::in_map(hc, wc, g.H, g.W)) r.v[c].load(xb + ((size_t)hc * g.W + wc) * g.C + c0);
                 else r.v[c].zero();
             }
         }
@@ -515,9 +503,9 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_kernel(const T* __restrict
         }
         gh = bt_group_sum<LPS>(gh); gw = bt_group_sum<LPS>(gw); gm = bt_group_sum<LPS>(gm);
         if (cl == 0 && q0.ok) {
-            const size_t o = (size_t)q0.m * 32;
-            raw_put<T>(graw, g.raw16, o + 2 * q0.tap, gh * q0.mask); raw_put<T>(graw, g.raw16, o + 2 * q0.tap + 1, gw * q0.mask);
-            raw_put<T>(graw, g.raw16, o + 18 + q0.tap, g.raw_mask ? gm : gm * q0.mask * (1.f - q0.mask));      // through the sigmoid of the mask logit
+            const size_t o = (size_t)q0.m * dcns::kRow;
+            raw_put<T>(graw, g.raw16, o + dcns::off_h(q0.tap), gh * q0.mask); raw_put<T>(graw, g.raw16, o + dcns::off_w(q0.tap), gw * q0.mask);
+            raw_put<T>(graw, g.raw16, o + dcns::mask_at(q0.tap), g.raw_mask ? gm : gm * q0.mask * (1.f - q0.mask));      // through the sigmoid of the mask logit
             if (q0.tap == 0) {
 #pragma unroll
                 for (int z = 27; z < 32; ++z) raw_put<T>(graw, g.raw16, o + z, 0.f);
@@ -586,19 +574,17 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_wgrad_kernel(const T* __re
     struct Pre { float oh, ow, mk; };
     auto prefetch = [&](const Loc& q) {
         Pre p = {0.f, 0.f, 0.f};
-        if (q.ok) { const float* r = om + q.m * 32; p.oh = r[2 * q.tap]; p.ow = r[2 * q.tap + 1]; p.mk = r[18 + q.tap]; }
+        if (q.ok) { const float* r = om + q.m * dcns::kRow; p.oh = r[dcns::off_h(q.tap)]; p.ow = r[dcns::off_w(q.tap)]; p.mk = r[dcns::mask_at(q.tap)]; }
         return p;
     };
     struct Geo { bool inside; int h0, w0; float lh, lw, mask; };
     auto geo = [&](const Loc& q, const Pre& p) {
         Geo e;
-        const int th = (q.tap * 11) >> 5, tw = q.tap - th * 3;
-        const float h = (float)(q.my - 1 + th) + p.oh, w = (float)(q.mx - 1 + tw) + p.ow;
+        const SampGeo sg = samp_geo(g, q.my, q.mx, q.tap, p.oh, p.ow);
         e.mask = p.mk;
-        e.inside = q.ok && h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W;
-        const float hf = floorf(h), wf = floorf(w);
-        e.lh = h - hf; e.lw = w - wf;
-        e.h0 = (int)fminf(fmaxf(hf, -4.f), 32000.f); e.w0 = (int)fminf(fmaxf(wf, -4.f), 32000.f);
+        e.inside = q.ok && sg.inside;
+        e.lh = sg.s.lh; e.lw = sg.s.lw;
+        e.h0 = sg.s.h0; e.w0 = sg.s.w0;
         return e;
     };
     struct Raw5 { Raw8<T> g, v[4]; };
@@ -609,7 +595,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_wgrad_kernel(const T* __re
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const int hc = e.h0 + (c >> 1), wc = e.w0 + (c & 1);
-                if (hc >= 0 && hc < g.H && wc >= 0 && wc < g.W) r.v[c].load(q.xb + ((size_t)hc * g.W + wc) * g.C + c0);
+                if (dcns::in_map(hc, wc, g.H, g.W)) r.v[c].load(q.xb + ((size_t)hc * g.W + wc) * g.C + c0);
                 else r.v[c].zero();
             }
         }
@@ -647,9 +633,9 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_wgrad_kernel(const T* __re
                 *reinterpret_cast<u32x4*>(stage + (tl * 4 + (cl >> 1)) * SF_TILE + l0.px * 32 + (cl & 1) * 16) = ElemTraits<T>::pack(cv);
                 gh = bt_group_sum<8>(gh); gw = bt_group_sum<8>(gw); gm = bt_group_sum<8>(gm);
                 if (cl == 0) {
-                    const size_t o = (size_t)l0.m * 32;
-                    raw_put<T>(graw, g.raw16, o + 2 * l0.tap, gh * e0.mask); raw_put<T>(graw, g.raw16, o + 2 * l0.tap + 1, gw * e0.mask);
-                    raw_put<T>(graw, g.raw16, o + 18 + l0.tap, g.raw_mask ? gm : gm * e0.mask * (1.f - e0.mask));
+                    const size_t o = (size_t)l0.m * dcns::kRow;
+                    raw_put<T>(graw, g.raw16, o + dcns::off_h(l0.tap), gh * e0.mask); raw_put<T>(graw, g.raw16, o + dcns::off_w(l0.tap), gw * e0.mask);
+                    raw_put<T>(graw, g.raw16, o + dcns::mask_at(l0.tap), g.raw_mask ? gm : gm * e0.mask * (1.f - e0.mask));
                     if (l0.tap == 0) {
 #pragma unroll
                         for (int z = 27; z < 32; ++z) raw_put<T>(graw, g.raw16, o + z, 0.f);
@@ -761,7 +747,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_tile_fly_kernel(const float* __re
         }
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            const int th = tap / 3, tw = tap - th * 3;
+            const dcns::Tap t = dcns::tap3x3(tap);
 #pragma unroll
             for (int round = 0; round < BT_ROUNDS; ++round) {
                 if (!valid[round]) continue;
@@ -770,17 +756,15 @@ __global__ __launch_bounds__(256) void dcn_bwd_tile_fly_kernel(const float* __re
                 const int my = ty0 - BT_D + wy, mx = tx0 - BT_D + wx;
                 const bool own = wy >= BT_D && wy < BT_D + BT_TH && wx >= BT_D && wx < BT_D + BT_TW;
                 const size_t m = (size_t)(mb + (long)my * g.W + mx);
-                const float h = (float)(my - 1 + th) + o[round][2 * tap], w = (float)(mx - 1 + tw) + o[round][2 * tap + 1];
-                const float mask = o[round][18 + tap];
-                if (!(h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W) || mask == 0.f) continue;
-                const float hf = floorf(h), wf = floorf(w);
-                const float lh = h - hf, lw = w - wf, hh = 1.f - lh, hw = 1.f - lw;
-                const int h0 = (int)hf, w0 = (int)wf;
+                const float h = dcns::pos3x3(my, t.th, o[round][dcns::off_h(tap)]), w = dcns::pos3x3(mx, t.tw, o[round][dcns::off_w(tap)]);
+                const float mask = o[round][dcns::mask_at(tap)];
+                if (!dcns::inside(h, w, g.H, g.W) || mask == 0.f) continue;
+                const dcns::Sample s = dcns::sample_inside(h, w);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int hc = h0 + (q >> 1), wc = w0 + (q & 1);
-                    const float wq = ((q >> 1) ? lh : hh) * ((q & 1) ? lw : hw) * mask;
-                    if (hc < 0 || hc >= g.H || wc < 0 || wc >= g.W || wq == 0.f) continue;
+                    const int hc = dcns::corner_h(s, q), wc = dcns::corner_w(s, q);
+                    const float wq = dcns::corner_weight(s, q) * mask;
+                    if (!dcns::in_map(hc, wc, g.H, g.W) || wq == 0.f) continue;
                     const int ly = hc - ty0, lx = wc - tx0;
                     if (ly >= 0 && ly < BT_TH && lx >= 0 && lx < BT_TW) {
                         const int p = ly * BT_TW + lx;
@@ -806,8 +790,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_tile_fly_kernel(const float* __re
                 const uint2 en = fstage[i];
                 const int q = (int)(en.x >> 28), emy = (int)((en.x >> 16) & 0xfff), emx = (int)((en.x >> 4) & 0xfff), etap = (int)(en.x & 15);
                 const size_t m = (size_t)(mb + (long)emy * g.W + emx);
-                const SampGeo sg = samp_geo(g, om + m * 32, emy, emx, etap);
-                far_entry(fbase + i, m, etap, sg.h0 + (q >> 1), sg.w0 + (q & 1), en.y);
+                const SampGeo sg = samp_geo(g, emy, emx, etap, om[m * dcns::kRow + dcns::off_h(etap)], om[m * dcns::kRow + dcns::off_w(etap)]);
+                far_entry(fbase + i, m, etap, dcns::corner_h(sg.s, q), dcns::corner_w(sg.s, q), en.y);
             }
         }
     }
@@ -1059,19 +1043,17 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_wgrad_fly_kernel(const T* 
     struct Pre { float oh, ow, mk; };
     auto prefetch = [&](const Loc& q) {
         Pre p = {0.f, 0.f, 0.f};
-        if (q.ok) { const float* r = om + q.m * 32; p.oh = r[2 * q.tap]; p.ow = r[2 * q.tap + 1]; p.mk = r[18 + q.tap]; }
+        if (q.ok) { const float* r = om + q.m * dcns::kRow; p.oh = r[dcns::off_h(q.tap)]; p.ow = r[dcns::off_w(q.tap)]; p.mk = r[dcns::mask_at(q.tap)]; }
         return p;
     };
     struct Geo { bool inside; int h0, w0; float lh, lw, mask; };
     auto geo = [&](const Loc& q, const Pre& p) {
         Geo e;
-        const int th = (q.tap * 11) >> 5, tw = q.tap - th * 3;
-        const float h = (float)(q.my - 1 + th) + p.oh, w = (float)(q.mx - 1 + tw) + p.ow;
+        const SampGeo sg = samp_geo(g, q.my, q.mx, q.tap, p.oh, p.ow);
         e.mask = p.mk;
-        e.inside = q.ok && h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W;
-        const float hf = floorf(h), wf = floorf(w);
-        e.lh = h - hf; e.lw = w - wf;
-        e.h0 = (int)fminf(fmaxf(hf, -4.f), 32000.f); e.w0 = (int)fminf(fmaxf(wf, -4.f), 32000.f);
+        e.inside = q.ok && sg.inside;
+        e.lh = sg.s.lh; e.lw = sg.s.lw;
+        e.h0 = sg.s.h0; e.w0 = sg.s.w0;
         return e;
     };
     struct Raw4 { Raw8<T> v[4]; };
@@ -1081,7 +1063,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_wgrad_fly_kernel(const T* 
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const int hc = e.h0 + (c >> 1), wc = e.w0 + (c & 1);
-                if (hc >= 0 && hc < g.H && wc >= 0 && wc < g.W) r.v[c].load(q.xb + ((size_t)hc * g.W + wc) * g.C + c0);
+                if (dcns::in_map(hc, wc, g.H, g.W)) r.v[c].load(q.xb + ((size_t)hc * g.W + wc) * g.C + c0);
                 else r.v[c].zero();
             }
         }
@@ -1172,9 +1154,9 @@ __global__ __launch_bounds__(256) void dcn_bwd_sample_wgrad_fly_kernel(const T* 
                 *reinterpret_cast<u32x4*>(stage + (tl * 4 + (cl >> 1)) * SF_TILE + l0.px * 32 + (cl & 1) * 16) = ElemTraits<T>::pack(cv);
                 gh = bt_group_sum<8>(gh); gw = bt_group_sum<8>(gw); gm = bt_group_sum<8>(gm);
                 if (cl == 0) {
-                    const size_t o = (size_t)l0.m * 32;
-                    raw_put<T>(graw, g.raw16, o + 2 * l0.tap, gh * e0.mask); raw_put<T>(graw, g.raw16, o + 2 * l0.tap + 1, gw * e0.mask);
-                    raw_put<T>(graw, g.raw16, o + 18 + l0.tap, g.raw_mask ? gm : gm * e0.mask * (1.f - e0.mask));
+                    const size_t o = (size_t)l0.m * dcns::kRow;
+                    raw_put<T>(graw, g.raw16, o + dcns::off_h(l0.tap), gh * e0.mask); raw_put<T>(graw, g.raw16, o + dcns::off_w(l0.tap), gw * e0.mask);
+                    raw_put<T>(graw, g.raw16, o + dcns::mask_at(l0.tap), g.raw_mask ? gm : gm * e0.mask * (1.f - e0.mask));
                     if (l0.tap == 0) {
 #pragma unroll
                         for (int z = 27; z < 32; ++z) raw_put<T>(graw, g.raw16, o + z, 0.f);

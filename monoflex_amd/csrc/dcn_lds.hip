@@ -30,6 +30,7 @@
 #include "err.h"
 #include "internal.h"
 #include "igemm.h"
+#include "dcn_sample_math.h"
 
 namespace mfx {
 
@@ -131,11 +132,11 @@ __global__ __launch_bounds__(256, TR == 8 ? 3 : 2) void dcn_lds_kernel(const TX*
     float odh[TPT], odw[TPT], omk[TPT];
     const int tap0 = TPT * tg;
     if constexpr (!OF) {
-        const float* r = om + ((size_t)(b * g.H + min(yo, g.H - 1)) * g.W + min(xo, g.W - 1)) * 32;
+        const float* r = om + ((size_t)(b * g.H + min(yo, g.H - 1)) * g.W + min(xo, g.W - 1)) * dcns::kRow;
 #pragma unroll
         for (int tt = 0; tt < TPT; ++tt) {
             const int tap = min(tap0 + tt, 8);
-            odh[tt] = r[2 * tap]; odw[tt] = r[2 * tap + 1]; omk[tt] = r[18 + tap];
+            odh[tt] = r[dcns::off_h(tap)]; odw[tt] = r[dcns::off_w(tap)]; omk[tt] = r[dcns::mask_at(tap)];
         }
         patch_fetch(0);
     } else {
@@ -207,11 +208,11 @@ __global__ __launch_bounds__(256, TR == 8 ? 3 : 2) void dcn_lds_kernel(const TX*
 #pragma unroll
                 for (int tt = 0; tt < TPT; ++tt) {
                     const int tap = min(tap0 + tt, 8);
-                    const float2 d2 = *reinterpret_cast<const float2*>(tbuf + xl * TLD + 2 * tap);
-                    odh[tt] = d2.x; odw[tt] = d2.y; omk[tt] = tbuf[xl * TLD + 18 + tap];
+                    const float2 d2 = *reinterpret_cast<const float2*>(tbuf + xl * TLD + dcns::off_h(tap));
+                    odh[tt] = d2.x; odw[tt] = d2.y; omk[tt] = tbuf[xl * TLD + dcns::mask_at(tap)];
                 }
                 if (oa.om_out && own_ok && tg == 0) {
-                    float* o = oa.om_out + ((size_t)(b * g.H + yo) * g.W + xo) * 32;
+                    float* o = oa.om_out + ((size_t)(b * g.H + yo) * g.W + xo) * dcns::kRow;
 #pragma unroll
                     for (int q = 0; q < 32; q += 4) *reinterpret_cast<f32x4*>(o + q) = *reinterpret_cast<const f32x4*>(tbuf + xl * TLD + q);
                 }
@@ -229,16 +230,13 @@ __global__ __launch_bounds__(256, TR == 8 ? 3 : 2) void dcn_lds_kernel(const TX*
         // this lane's tt-th tap: tt + TPT * tg (OWN == 2: lanes of the second group start at tap 5 and have no fifth one)
         const int tap = tap0 + tt;
         const bool has = tap < 9;
-        const float dh = odh[tt], dw = odw[tt];
         const float mk = (own_ok && has) ? omk[tt] : 0.f;
-        const int th = tap / 3, tw = tap - th * 3;
-        const float h = (float)(yo - 1 + th) + dh, w = (float)(xo - 1 + tw) + dw;
-        const bool inside = h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W;
-        const float hf = floorf(h), wf_ = floorf(w);
-        const float lh = h - hf, lw = w - wf_, hh = 1.f - lh, hw_ = 1.f - lw;
-        const float m_ = inside ? mk : 0.f;
-        // clamp before the int conversion: a wild offset must not overflow (the sample is outside the image then: weight 0)
-        const int h0 = (int)fminf(fmaxf(hf, -24.f), 30000.f), w0 = (int)fminf(fmaxf(wf_, -24.f), 30000.f);
+        const dcns::Tap t = dcns::tap3x3(tap);
+        const float h = dcns::pos3x3(yo, t.th, odh[tt]), w = dcns::pos3x3(xo, t.tw, odw[tt]);
+        const dcns::Sample s = dcns::sample(h, w);
+        const float lh = s.lh, lw = s.lw, hh = s.hh, hw_ = s.hw;
+        const int h0 = s.h0, w0 = s.w0;                       // in [-24, 30000]: the far packing below needs h0 + 32 >= 0 and w0 + 32 < 2^15
+        const float m_ = dcns::inside(h, w, g.H, g.W) ? mk : 0.f;
         uint32_t wa = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(hh * hw_ * m_, hh * lw * m_));
         uint32_t wb_ = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(lh * hw_ * m_, lh * lw * m_));
         const int ry = h0 - py0, rx = w0 - px0;
@@ -525,13 +523,13 @@ __global__ __launch_bounds__(256, 2) void dcn_lds_split_kernel(const float* __re
 
     // ---- phase G: geometry of this lane's taps -> table
     {
-        const float* r = om + ((size_t)(b * g.H + min(yo, g.H - 1)) * g.W + min(xo, g.W - 1)) * 32;
+        const float* r = om + ((size_t)(b * g.H + min(yo, g.H - 1)) * g.W + min(xo, g.W - 1)) * dcns::kRow;
         const int tap0 = TPT * tg;
         float odh[TPT], odw[TPT], omk[TPT];
 #pragma unroll
         for (int tt = 0; tt < TPT; ++tt) {
             const int tap = min(tap0 + tt, 8);
-            odh[tt] = r[2 * tap]; odw[tt] = r[2 * tap + 1]; omk[tt] = r[18 + tap];
+            odh[tt] = r[dcns::off_h(tap)]; odw[tt] = r[dcns::off_w(tap)]; omk[tt] = r[dcns::mask_at(tap)];
         }
         patch_load(0);
 #pragma unroll
@@ -539,19 +537,18 @@ __global__ __launch_bounds__(256, 2) void dcn_lds_split_kernel(const float* __re
             const int tap = tap0 + tt;
             const bool has = tap < 9;
             const float mk = (own_ok && has) ? omk[tt] : 0.f;
-            const int th = tap / 3, tw = tap - th * 3;
-            const float h = (float)(yo - 1 + th) + odh[tt], w = (float)(xo - 1 + tw) + odw[tt];
-            const bool inside = h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W;
-            const float hf = floorf(h), wf_ = floorf(w);
-            const float m_ = inside ? mk : 0.f;
-            const int h0 = (int)fminf(fmaxf(hf, -24.f), 30000.f), w0 = (int)fminf(fmaxf(wf_, -24.f), 30000.f);
+            const dcns::Tap t = dcns::tap3x3(tap);
+            const float h = dcns::pos3x3(yo, t.th, odh[tt]), w = dcns::pos3x3(xo, t.tw, odw[tt]);
+            const dcns::Sample s = dcns::sample(h, w);
+            const int h0 = s.h0, w0 = s.w0;
+            const float m_ = dcns::inside(h, w, g.H, g.W) ? mk : 0.f;
             const int ry = h0 - py0, rx = w0 - px0;
             const bool in_patch = ry >= 0 && ry + 1 < PH && rx >= 0 && rx + 1 < PW;
             const bool far = m_ != 0.f && !in_patch;
             uint32_t base = in_patch ? (uint32_t)((ry * PW + rx) * PB) : 0u;
             if (far) base = 0x80000000u | (uint32_t)(h0 + 32) | ((uint32_t)(w0 + 32) << 16);
             // the mask of a far sample is stored NEGATED: the loop clamps it to zero, the far pass takes its magnitude
-            if (has) *reinterpret_cast<f32x4*>(smem + GT_OFF + (tap * NPIX + opix) * 16) = f32x4{h - hf, w - wf_, far ? -m_ : m_, __uint_as_float(base)};
+            if (has) *reinterpret_cast<f32x4*>(smem + GT_OFF + (tap * NPIX + opix) * 16) = f32x4{s.lh, s.lw, far ? -m_ : m_, __uint_as_float(base)};
         }
         if (tid < FM) *reinterpret_cast<f32x4*>(smem + GT_OFF + (NG + 16 * tid) * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
     }

@@ -27,6 +27,7 @@
 #include "err.h"
 #include "internal.h"
 #include "igemm.h"
+#include "dcn_sample_math.h"
 
 namespace mfx {
 
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void dcn_patch_kernel(const TX* __restrict_
     const bool own_ok = yo < g.H && xo < g.W;
     float omv[27];
     if constexpr (!OF) {
-        const float* r = om + ((size_t)(b * g.H + min(yo, g.H - 1)) * g.W + min(xo, g.W - 1)) * 32;
+        const float* r = om + ((size_t)(b * g.H + min(yo, g.H - 1)) * g.W + min(xo, g.W - 1)) * dcns::kRow;
 #pragma unroll
         for (int q = 0; q < 24; q += 4) {
             const f32x4 t = *reinterpret_cast<const f32x4*>(r + q);
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void dcn_patch_kernel(const TX* __restrict_
                 }
                 omv[24] = tbuf[xl * TLD + 24]; omv[25] = tbuf[xl * TLD + 25]; omv[26] = tbuf[xl * TLD + 26];
                 if (oa.om_out && own_ok) {
-                    float* o = oa.om_out + ((size_t)(b * g.H + yo) * g.W + xo) * 32;
+                    float* o = oa.om_out + ((size_t)(b * g.H + yo) * g.W + xo) * dcns::kRow;
 #pragma unroll
                     for (int q = 0; q < 32; q += 4) *reinterpret_cast<f32x4*>(o + q) = *reinterpret_cast<const f32x4*>(tbuf + xl * TLD + q);
                 }
@@ -203,15 +204,13 @@ __global__ __launch_bounds__(256, 2) void dcn_patch_kernel(const TX* __restrict_
     // per-fragment sampling state of the current tap (consumer side)
     int cb[FM][4]; uint32_t cwa[FM], cwb[FM]; int chw[FM]; bool inp[FM];
     auto geom = [&](int tap) {
-        const int th = tap / 3, tw = tap - th * 3;
-        const float dh = omv[2 * tap], dw = omv[2 * tap + 1], mk = own_ok ? omv[18 + tap] : 0.f;
-        const float h = (float)(yo - 1 + th) + dh, w = (float)(xo - 1 + tw) + dw;
-        const bool inside = h > -1.f && w > -1.f && h < (float)g.H && w < (float)g.W;
-        const float hf = floorf(h), wf_ = floorf(w);
-        const float lh = h - hf, lw = w - wf_, hh = 1.f - lh, hw_ = 1.f - lw;
-        const float m_ = inside ? mk : 0.f;
-        // clamp before the int conversion: a wild offset must not overflow (the sample is outside the image then: weight 0)
-        const int h0 = (int)fminf(fmaxf(hf, -24.f), 30000.f), w0 = (int)fminf(fmaxf(wf_, -24.f), 30000.f);
+        const dcns::Tap t = dcns::tap3x3(tap);
+        const float mk = own_ok ? omv[dcns::mask_at(tap)] : 0.f;
+        const float h = dcns::pos3x3(yo, t.th, omv[dcns::off_h(tap)]), w = dcns::pos3x3(xo, t.tw, omv[dcns::off_w(tap)]);
+        const dcns::Sample s = dcns::sample(h, w);
+        const float lh = s.lh, lw = s.lw, hh = s.hh, hw_ = s.hw;
+        const int h0 = s.h0, w0 = s.w0;                       // in [-24, 30000]: the packing below needs h0 + 32 >= 0 and w0 + 32 < 2^15
+        const float m_ = dcns::inside(h, w, g.H, g.W) ? mk : 0.f;
         const uint32_t wa = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(hh * hw_ * m_, hh * lw * m_));
         const uint32_t wb_ = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(lh * hw_ * m_, lh * lw * m_));
         const int hw = (h0 + 32) | ((w0 + 32) << 16);

@@ -19,6 +19,7 @@
 #include "../../include/monoflex_hip.h"
 #include "err.h"
 #include "common.h"
+#include "dcn_sample_math.h"
 
 namespace mfx {
 
@@ -43,23 +44,18 @@ __global__ __launch_bounds__(256, 4) void dcn_sample_kernel(const T* __restrict_
         const int pl = it / 9, tap = it - pl * 9;
         const int yo = ty * TH + pl / TW, xo = tx * TW + pl % TW;
         const bool ok = yo < H && xo < W;
-        const float* r = om + ((size_t)(b * H + min(yo, H - 1)) * W + min(xo, W - 1)) * 32;
-        const float dh = r[2 * tap], dw = r[2 * tap + 1], mk = ok ? r[18 + tap] : 0.f;
-        const int th = tap / 3, tw = tap - th * 3;
-        const float h = (float)(yo - 1 + th) + dh, w = (float)(xo - 1 + tw) + dw;
-        const bool inside = h > -1.f && w > -1.f && h < (float)H && w < (float)W;
-        const float hf = floorf(h), wf = floorf(w);
-        const float lh = h - hf, lw = w - wf, hh = 1.f - lh, hw = 1.f - lw;
-        const float m_ = inside ? mk : 0.f;
-        // clamp before the int conversion: a wild offset must not overflow (the sample is outside the image then: weight 0)
-        const int h0 = (int)fminf(fmaxf(hf, -2.f), 30000.f), w0 = (int)fminf(fmaxf(wf, -2.f), 30000.f);
-        const bool t0 = h0 >= 0 && h0 < H, t1 = h0 + 1 >= 0 && h0 + 1 < H, l0 = w0 >= 0 && w0 < W, l1 = w0 + 1 >= 0 && w0 + 1 < W;
-        const int ch0 = min(max(h0, 0), H - 1), ch1 = min(max(h0 + 1, 0), H - 1), cw0 = min(max(w0, 0), W - 1), cw1 = min(max(w0 + 1, 0), W - 1);
+        const float* r = om + ((size_t)(b * H + min(yo, H - 1)) * W + min(xo, W - 1)) * dcns::kRow;
+        const float mk = ok ? r[dcns::mask_at(tap)] : 0.f;
+        const dcns::Tap t = dcns::tap3x3(tap);
+        const float h = dcns::pos3x3(yo, t.th, r[dcns::off_h(tap)]), w = dcns::pos3x3(xo, t.tw, r[dcns::off_w(tap)]);
+        const bool inside = dcns::inside(h, w, H, W);
+        const dcns::Sample s = dcns::sample(h, w);
         const int rb = b * H;
-        gw[it][0] = (t0 && l0) ? hh * hw * m_ : 0.f; go[it][0] = ((rb + ch0) * W + cw0) * LDP + tap * N;
-        gw[it][1] = (t0 && l1) ? hh * lw * m_ : 0.f; go[it][1] = ((rb + ch0) * W + cw1) * LDP + tap * N;
-        gw[it][2] = (t1 && l0) ? lh * hw * m_ : 0.f; go[it][2] = ((rb + ch1) * W + cw0) * LDP + tap * N;
-        gw[it][3] = (t1 && l1) ? lh * lw * m_ : 0.f; go[it][3] = ((rb + ch1) * W + cw1) * LDP + tap * N;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            gw[it][q] = dcns::corner_valid(s, inside, q, H, W) ? dcns::corner_weight(s, q) * mk : 0.f;
+            go[it][q] = ((rb + dcns::clamp_idx(dcns::corner_h(s, q), H)) * W + dcns::clamp_idx(dcns::corner_w(s, q), W)) * LDP + tap * N;
+        }
     }
     __syncthreads();
 
