@@ -339,6 +339,26 @@ int mfx_decode_boxes_mode(const float* hmap, int ld, int reg_off, const float* s
                           int ncls, int B, int H, int W, int K, const float* calib, const int32_t* pad,
                           const int32_t* img_size, float threshold, int depth_mode, float* det, float* topk, int32_t* valid,
                           void* stream);
+/* The same with the head settings the model was trained with (anno_encoder.py:124-140 decode_depth, :221-243 decode_dimension,
+ * detector_infer.py:223-229 the score rule) instead of the runs/monoflex.yaml ones mfx_decode_boxes_mode has built in (KITTI DIMENSION_MEAN,
+ * exp dimensions without std, inv_sigmoid depth in [0.1, 100], uncertainty-scaled score, three classes), which is this entry with those values.
+ * `cfg` is a host pointer, copied by value into the launch (no allocation, no synchronisation, hipGraph-capturable).  1 <= ncls <= 3, K <= 256;
+ * the class of a row is its position in the (ncls K) list / K and selects the row of dim_mean / dim_std.
+ * unc: optional fp32 [B][K][2] = estimated_depth_error (the sigma of the chosen depth), uncertainty_conf = 1 - clamp(sigma, 0.01, 1); both 0
+ * when uncertainty_as_conf == 0 (the reference reports None there, and the score column is then the raw score). */
+typedef struct mfx_decode_cfg {
+    float dim_mean[9], dim_std[9];     /* (l,h,w) per class, rows >= ncls unused */
+    float depth_ref[2], depth_range[2];
+    float down_ratio, eps;             /* 4, 1e-3 */
+    int depth_decode;                  /* 0 exp, 1 linear, 2 inv_sigmoid: mfx_object_loss_cfg.depth_mode's numbering */
+    int dim_exp, dim_use_std;          /* DIMENSION_REG[0] == 'exp', DIMENSION_REG[2] */
+    int uncertainty_as_conf;           /* TEST.UNCERTAINTY_AS_CONFIDENCE */
+    int output_depth;                  /* MFX_DEPTH_* */
+} mfx_decode_cfg;
+int mfx_decode_boxes_cfg(const float* hmap, int ld, int reg_off, const float* scores, const int32_t* index,
+                         int ncls, int B, int H, int W, int K, const float* calib, const int32_t* pad,
+                         const int32_t* img_size, float threshold, const mfx_decode_cfg* cfg, float* det, float* topk, int32_t* valid,
+                         float* unc, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (3) training path (reference: autograd over nn.Conv2d / BatchNorm2d / MaxPool2d / ConvTranspose2d and

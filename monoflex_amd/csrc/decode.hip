@@ -5,6 +5,7 @@
 #include "../../include/monoflex_hip.h"
 #include "common.h"
 #include "err.h"
+#include <cmath>
 
 namespace mfx {
 
@@ -276,20 +277,13 @@ __global__ __launch_bounds__(512) void decode_topk_merge_kernel(const float* can
     }
 }
 
-struct DecodeConst {
-    float dim_mean[3][3];     // (l,h,w) per class, config/defaults.py:206-208
-    float depth_min, depth_max;
-    float down_ratio, eps;
-    int depth_mode;           // MFX_DEPTH_* (detector_infer.py:149-198 `output_depth`)
-};
-
 // key2channel offsets of runs/monoflex.yaml:27-28
 enum { R_2D = 0, R_OFF3D = 4, R_KPT = 6, R_KPT_UNC = 26, R_DIM3D = 29, R_ORI_CLS = 32, R_ORI_OFF = 40, R_DEPTH = 48, R_DEPTH_UNC = 49, R_TOTAL = 50 };
 
 __global__ __launch_bounds__(256) void decode_boxes_kernel(const float* hmap, int ld, int reg_off, const float* scores, const int* index,
                                                            int ncls, int H, int W, int K, const float* calib, const int* pad,
-                                                           const int* img_size, float threshold, DecodeConst dc,
-                                                           float* det, float* topk, int* valid) {
+                                                           const int* img_size, float threshold, mfx_decode_cfg dc,
+                                                           float* det, float* topk, int* valid, float* unc) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* cs = reinterpret_cast<float*>(smem_raw);          // [ncls*K]
     int* ci = reinterpret_cast<int*>(cs + ncls * K);         // [ncls*K]
@@ -326,14 +320,20 @@ __global__ __launch_bounds__(256) void decode_boxes_kernel(const float* hmap, in
     x1 = fminf(fmaxf(x1, 0.f), wmax); x2 = fminf(fmaxf(x2, 0.f), wmax);
     y1 = fminf(fmaxf(y1, 0.f), hmax); y2 = fminf(fmaxf(y2, 0.f), hmax);
 
-    // decode_dimension (anno_encoder.py:221-243): exp(offset) * mean[cls], order (l,h,w)
-    const float dl = expf(r[R_DIM3D + 0]) * dc.dim_mean[cls][0];
-    const float dh = expf(r[R_DIM3D + 1]) * dc.dim_mean[cls][1];
-    const float dw = expf(r[R_DIM3D + 2]) * dc.dim_mean[cls][2];
+    // decode_dimension (anno_encoder.py:221-243), order (l,h,w): exp(offset) or the offset, then * std[cls] + mean[cls] or * mean[cls]
+    auto dim = [&](int i) {
+        const float off = dc.dim_exp ? expf(r[R_DIM3D + i]) : r[R_DIM3D + i];
+        return dc.dim_use_std ? off * dc.dim_std[cls * 3 + i] + dc.dim_mean[cls * 3 + i] : off * dc.dim_mean[cls * 3 + i];
+    };
+    const float dl = dim(0), dh = dim(1), dw = dim(2);
 
-    // decode_depth inv_sigmoid (anno_encoder.py:124-140)
-    float d0 = 1.f / (1.f / (1.f + expf(-r[R_DEPTH]))) - 1.f;
-    d0 = fminf(fmaxf(d0, dc.depth_min), dc.depth_max);
+    // decode_depth (anno_encoder.py:124-140): exp / linear around DEPTH_REFERENCE / inv_sigmoid, then the DEPTH_RANGE clamp
+    const float depth_min = dc.depth_range[0], depth_max = dc.depth_range[1];
+    float d0;
+    if (dc.depth_decode == 0) d0 = expf(r[R_DEPTH]);
+    else if (dc.depth_decode == 1) d0 = r[R_DEPTH] * dc.depth_ref[1] + dc.depth_ref[0];
+    else d0 = 1.f / (1.f / (1.f + expf(-r[R_DEPTH]))) - 1.f;
+    d0 = fminf(fmaxf(d0, depth_min), depth_max);
     const float u0 = expf(r[R_DEPTH_UNC]);
 
     // decode_depth_from_keypoints_batch (anno_encoder.py:187-219); keypoint k = (r[6+2k], r[7+2k])
@@ -342,34 +342,34 @@ __global__ __launch_bounds__(256) void decode_boxes_kernel(const float* hmap, in
     float d1 = kdepth(ky(8) - ky(9));
     float d2 = (kdepth(ky(0) - ky(4)) + kdepth(ky(2) - ky(6))) / 2.f;
     float d3 = (kdepth(ky(1) - ky(5)) + kdepth(ky(3) - ky(7))) / 2.f;
-    d1 = fminf(fmaxf(d1, dc.depth_min), dc.depth_max);
-    d2 = fminf(fmaxf(d2, dc.depth_min), dc.depth_max);
-    d3 = fminf(fmaxf(d3, dc.depth_min), dc.depth_max);
+    d1 = fminf(fmaxf(d1, depth_min), depth_max);
+    d2 = fminf(fmaxf(d2, depth_min), depth_max);
+    d3 = fminf(fmaxf(d3, depth_min), depth_max);
     const float u1 = expf(r[R_KPT_UNC + 0]), u2 = expf(r[R_KPT_UNC + 1]), u3 = expf(r[R_KPT_UNC + 2]);
 
     // which depth leaves the four estimates, and the uncertainty that scales the score with it (detector_infer.py:149-198 `output_depth`)
     float depth, sigma;
-    if (dc.depth_mode == MFX_DEPTH_SOFT) {                    // 'soft' (:186-192; runs/monoflex.yaml)
+    if (dc.output_depth == MFX_DEPTH_SOFT) {                    // 'soft' (:186-192; runs/monoflex.yaml)
         float w0 = 1.f / u0, w1 = 1.f / u1, w2 = 1.f / u2, w3 = 1.f / u3;
         const float ws = ((w0 + w1) + w2) + w3;
         w0 /= ws; w1 /= ws; w2 /= ws; w3 /= ws;
         depth = ((d0 * w0 + d1 * w1) + d2 * w2) + d3 * w3;
         sigma = ((w0 * u0 + w1 * u1) + w2 * u2) + w3 * u3;
-    } else if (dc.depth_mode == MFX_DEPTH_HARD) {             // 'hard' (:180-184): the estimate of the largest weight 1 / u (first of equals, as argmax)
+    } else if (dc.output_depth == MFX_DEPTH_HARD) {             // 'hard' (:180-184): the estimate of the largest weight 1 / u (first of equals, as argmax)
         const float w0 = 1.f / u0, w1 = 1.f / u1, w2 = 1.f / u2, w3 = 1.f / u3;
         depth = d0; float wb = w0;
         if (w1 > wb) { wb = w1; depth = d1; }
         if (w2 > wb) { wb = w2; depth = d2; }
         if (w3 > wb) { wb = w3; depth = d3; }
         sigma = fminf(fminf(u0, u1), fminf(u2, u3));
-    } else if (dc.depth_mode == MFX_DEPTH_MEAN) {             // 'mean' (:194-198)
+    } else if (dc.output_depth == MFX_DEPTH_MEAN) {             // 'mean' (:194-198)
         depth = (((d0 + d1) + d2) + d3) / 4.f; sigma = (((u0 + u1) + u2) + u3) / 4.f;
-    } else if (dc.depth_mode == MFX_DEPTH_DIRECT) {           // 'direct' (:149-152)
+    } else if (dc.output_depth == MFX_DEPTH_DIRECT) {           // 'direct' (:149-152)
         depth = d0; sigma = u0;
-    } else if (dc.depth_mode == MFX_DEPTH_KEYPOINTS_AVG) {    // 'keypoints_avg' (:155-157)
+    } else if (dc.output_depth == MFX_DEPTH_KEYPOINTS_AVG) {    // 'keypoints_avg' (:155-157)
         depth = ((d1 + d2) + d3) / 3.f; sigma = ((u1 + u2) + u3) / 3.f;
-    } else if (dc.depth_mode == MFX_DEPTH_KEYPOINTS_CENTER) { depth = d1; sigma = u1; }   // (:159-161)
-    else if (dc.depth_mode == MFX_DEPTH_KEYPOINTS_02) { depth = d2; sigma = u2; }          // (:163-165)
+    } else if (dc.output_depth == MFX_DEPTH_KEYPOINTS_CENTER) { depth = d1; sigma = u1; }   // (:159-161)
+    else if (dc.output_depth == MFX_DEPTH_KEYPOINTS_02) { depth = d2; sigma = u2; }          // (:163-165)
     else { depth = d3; sigma = u3; }                                                         // 'keypoints_13' (:167-169)
 
     // decode_location_flatten (anno_encoder.py:142-155) + project_image_to_rect (kitti_utils.py:350-369)
@@ -396,7 +396,9 @@ __global__ __launch_bounds__(256) void decode_boxes_kernel(const float* hmap, in
     if (alpha < -kPi) alpha += 2.f * kPi;
 
     Y += dh / 2.f;                                            // detector_infer.py:215
-    const float final_score = score * (1.f - fminf(fmaxf(sigma, 0.01f), 1.f));   // :225-227
+    // the depth's uncertainty scales the score under TEST.UNCERTAINTY_AS_CONFIDENCE (:223-229); otherwise the raw score, and no uncertainty is reported
+    const float conf = 1.f - fminf(fmaxf(sigma, 0.01f), 1.f);
+    const float final_score = dc.uncertainty_as_conf ? score * conf : score;
 
     float* o = det + ((size_t)b * K + j) * 14;
     o[0] = (float)cls; o[1] = alpha; o[2] = x1; o[3] = y1; o[4] = x2; o[5] = y2;
@@ -405,6 +407,10 @@ __global__ __launch_bounds__(256) void decode_boxes_kernel(const float* hmap, in
     float* t = topk + ((size_t)b * K + j) * 5;
     t[0] = score; t[1] = (float)idx; t[2] = (float)cls; t[3] = py; t[4] = px;
     valid[b * K + j] = score >= threshold ? 1 : 0;
+    if (unc) {                                                // [estimated_depth_error, uncertainty_conf]
+        unc[((size_t)b * K + j) * 2 + 0] = dc.uncertainty_as_conf ? sigma : 0.f;
+        unc[((size_t)b * K + j) * 2 + 1] = dc.uncertainty_as_conf ? conf : 0.f;
+    }
 }
 
 }  // namespace mfx
@@ -462,12 +468,34 @@ extern "C" int mfx_decode_boxes_mode(const float* hmap, int ld, int reg_off, con
     if (!hmap || !scores || !index || !calib || !pad || !img_size || !det || !topk || !valid)
         return mfx_fail(MFX_ERR_ARG, "decode_boxes: null pointer");
     if (K > 256 || ncls != 3) return mfx_fail(MFX_ERR_UNSUPPORTED, "decode_boxes: K <= 256, 3 classes (dimension means)");
+    // the runs/monoflex.yaml decode: KITTI DIMENSION_MEAN (config/defaults.py:206-208), exp dimensions without std, inv_sigmoid depth in [0.1, 100],
+    // uncertainty-scaled score
+    const mfx_decode_cfg cfg = {{3.8840f, 1.5261f, 1.6286f, 0.8423f, 1.7607f, 0.6602f, 1.7635f, 1.7372f, 0.5968f},
+                                {0.4259f, 0.1367f, 0.1022f, 0.2349f, 0.1133f, 0.1427f, 0.1766f, 0.0948f, 0.1242f},
+                                {26.494627f, 16.05988f}, {0.1f, 100.f}, 4.f, 1e-3f, 2, 1, 0, 1, depth_mode};
+    return mfx_decode_boxes_cfg(hmap, ld, reg_off, scores, index, ncls, B, H, W, K, calib, pad, img_size, threshold, &cfg, det, topk, valid, nullptr, stream);
+}
+
+extern "C" int mfx_decode_boxes_cfg(const float* hmap, int ld, int reg_off, const float* scores, const int32_t* index,
+                                    int ncls, int B, int H, int W, int K, const float* calib, const int32_t* pad,
+                                    const int32_t* img_size, float threshold, const mfx_decode_cfg* cfg, float* det, float* topk, int32_t* valid,
+                                    float* unc, void* stream) {
+    if (!cfg) return mfx_fail(MFX_ERR_ARG, "decode_boxes_cfg: null cfg");
+    if (!hmap || !scores || !index || !calib || !pad || !img_size || !det || !topk || !valid)
+        return mfx_fail(MFX_ERR_ARG, "decode_boxes_cfg: null pointer");
+    if (cfg->depth_decode < 0 || cfg->depth_decode > 2) return mfx_fail(MFX_ERR_ARG, "decode_boxes_cfg: depth_decode must be 0 (exp), 1 (linear) or 2 (inv_sigmoid)");
+    if (cfg->output_depth < MFX_DEPTH_SOFT || cfg->output_depth > MFX_DEPTH_KEYPOINTS_13)
+        return mfx_fail(MFX_ERR_ARG, "decode_boxes_cfg: output_depth must be one of MFX_DEPTH_*");
+    if (!std::isfinite(cfg->depth_range[0]) || !std::isfinite(cfg->depth_range[1]) || cfg->depth_range[0] > cfg->depth_range[1])
+        return mfx_fail(MFX_ERR_ARG, "decode_boxes_cfg: depth_range must be finite with depth_range[0] <= depth_range[1]");
+    if (ncls < 1 || ncls > 3) return mfx_fail(MFX_ERR_ARG, "decode_boxes_cfg: need 1 <= ncls <= 3 (rows of dim_mean / dim_std)");
+    if (K < 1 || K > 256) return mfx_fail(MFX_ERR_ARG, "decode_boxes_cfg: need 1 <= K <= 256");
+    if (B < 0 || H < 1 || W < 1 || ld < R_TOTAL || reg_off < 0 || reg_off + R_TOTAL > ld)
+        return mfx_fail(MFX_ERR_ARG, "decode_boxes_cfg: need B >= 0, H, W >= 1 and the 50 regression channels inside a row (reg_off + 50 <= ld)");
     if (B == 0) return MFX_OK;
-    DecodeConst dc = {{{3.8840f, 1.5261f, 1.6286f}, {0.8423f, 1.7607f, 0.6602f}, {1.7635f, 1.7372f, 0.5968f}},
-                      0.1f, 100.f, 4.f, 1e-3f, depth_mode};
     const size_t smem = (size_t)ncls * K * 8 + (size_t)K * 4;
     hipLaunchKernelGGL(decode_boxes_kernel, dim3(B), dim3(256), smem, reinterpret_cast<hipStream_t>(stream),
-                       hmap, ld, reg_off, scores, index, ncls, H, W, K, calib, pad, img_size, threshold, dc, det, topk, valid);
+                       hmap, ld, reg_off, scores, index, ncls, H, W, K, calib, pad, img_size, threshold, *cfg, det, topk, valid, unc);
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }

@@ -116,6 +116,12 @@ class ObjectLossCfg(ctypes.Structure):                          # mfx_object_los
                               "separate_trunc", "trunc_log", "modify_invalid")] + [("ch", c_int * 9)]
 
 
+class DecodeCfg(ctypes.Structure):                              # mfx_decode_cfg
+    _fields_ = [("dim_mean", c_float * 9), ("dim_std", c_float * 9), ("depth_ref", c_float * 2), ("depth_range", c_float * 2),
+                ("down_ratio", c_float), ("eps", c_float)] + \
+        [(n, c_int) for n in ("depth_decode", "dim_exp", "dim_use_std", "uncertainty_as_conf", "output_depth")]
+
+
 # every symbol include/monoflex_hip.h declares: name -> (restype, argtypes)
 _P, _I, _F, _S = c_void_p, c_int, c_float, c_size_t
 SYMBOLS = {
@@ -200,10 +206,51 @@ SYMBOLS = {
     "mfx_kitti_eval_match_pass2": (_I, [ctypes.POINTER(KittiEvalDesc), _P]),
     "mfx_decode_boxes": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P]),
     "mfx_decode_boxes_mode": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _P, _P, _P]),
+    "mfx_decode_boxes_cfg": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.POINTER(DecodeCfg), _P, _P, _P, _P, _P]),
 }
 
 # mfx_decode_boxes_mode's depth_mode (include/monoflex_hip.h MFX_DEPTH_*), by the reference's `output_depth` names (detector_infer.py:149-198)
 DEPTH_MODES = {"soft": 0, "hard": 1, "mean": 2, "direct": 3, "keypoints_avg": 4, "keypoints_center": 5, "keypoints_02": 6, "keypoints_13": 7}
+
+DEPTH_DECODES = {"exp": 0, "linear": 1, "inv_sigmoid": 2}      # mfx_decode_cfg.depth_decode = mfx_object_loss_cfg.depth_mode (anno_encoder.py:124-140)
+
+
+def head_decode_settings(cfg):
+    """The head settings that decide how a regression row becomes a box (reference Anno_Encoder.__init__, anno_encoder.py:25-33,45), read
+    from a config ONCE for both users: the loss evaluator (mfx_object_loss_cfg) and the post-processor (mfx_decode_cfg) take them from here,
+    so that a model cannot train under one rule and decode under another."""
+    H = cfg.MODEL.HEAD
+    return dict(depth_mode=H.DEPTH_MODE, depth_range=None if H.DEPTH_RANGE is None else tuple(float(v) for v in H.DEPTH_RANGE),
+                depth_ref=tuple(float(v) for v in H.DEPTH_REFERENCE),
+                dim_mean=tuple(tuple(float(v) for v in row) for row in H.DIMENSION_MEAN),
+                dim_std=tuple(tuple(float(v) for v in row) for row in H.DIMENSION_STD),
+                dim_modes=list(H.DIMENSION_REG), down_ratio=cfg.MODEL.BACKBONE.DOWN_RATIO, eps=1e-3)
+
+
+def fill_decode_settings(c, s):
+    """Write the settings of head_decode_settings() into the fields ObjectLossCfg and DecodeCfg share (dim_mean, dim_std, depth_ref,
+    depth_range, down_ratio, eps, dim_exp, dim_use_std); the depth rule's number (DEPTH_DECODES) is returned for the field each struct
+    names its own way."""
+    for name in ("dim_mean", "dim_std"):
+        flat = [v for row in s[name] for v in row]
+        if len(flat) > 9:
+            raise ValueError("%s: at most three (l, h, w) rows" % name)
+        for i, v in enumerate(flat):
+            getattr(c, name)[i] = v
+    c.depth_ref[0], c.depth_ref[1] = s["depth_ref"]
+    c.depth_range[0], c.depth_range[1] = s["depth_range"]
+    c.down_ratio, c.eps = float(s["down_ratio"]), float(s["eps"])
+    c.dim_exp, c.dim_use_std = int(s["dim_modes"][0] == 'exp'), int(bool(s["dim_modes"][2]))
+    return DEPTH_DECODES[s["depth_mode"]]
+
+
+def decode_cfg(settings, uncertainty_as_conf, output_depth="soft"):
+    """mfx_decode_cfg from head_decode_settings() + TEST.UNCERTAINTY_AS_CONFIDENCE + the reference's `output_depth` name."""
+    c = DecodeCfg()
+    c.depth_decode = fill_decode_settings(c, settings)
+    c.uncertainty_as_conf, c.output_depth = int(bool(uncertainty_as_conf)), DEPTH_MODES[output_depth]
+    return c
+
 
 _lib = None
 

@@ -32,23 +32,31 @@ class PostProcessor(nn.Module):
         self.output_depth = cfg.MODEL.HEAD.OUTPUT_DEPTH
         self.uncertainty_as_conf = cfg.TEST.UNCERTAINTY_AS_CONFIDENCE
         self.num_classes = len(cfg.DATASETS.DETECT_CLASSES)
-        keys = key2channel.keys
+        # What the decode kernel cannot do is refused; every head setting the loss evaluator accepts (DEPTH_MODE, DEPTH_REFERENCE,
+        # DEPTH_RANGE, DIMENSION_REG, DIMENSION_MEAN / _STD) and TEST.UNCERTAINTY_AS_CONFIDENCE reach it through mfx_decode_cfg.
         want = ['2d_dim', '3d_offset', 'corner_offset', 'corner_uncertainty', '3d_dim', 'ori_cls', 'ori_offset',
                 'depth', 'depth_uncertainty']
-        ok = (keys == want and key2channel.channels == [4, 2, 20, 3, 3, 8, 8, 1, 1] and (self.output_depth in L.DEPTH_MODES or self.output_depth == 'oracle')
-              and self.uncertainty_as_conf and cfg.MODEL.HEAD.DEPTH_MODE == 'inv_sigmoid'
-              and list(cfg.MODEL.HEAD.DIMENSION_REG) == ['exp', True, False] and cfg.INPUT.ORIENTATION == 'multi-bin'
-              and cfg.MODEL.BACKBONE.DOWN_RATIO == 4 and self.num_classes == 3)
-        # constants compiled into mfx_decode_boxes (decode.hip DecodeConst; reference config/defaults.py:175,206-208): a config
-        # that changes them would train with its own values and decode with the built-in ones, so it is refused
-        built_in_mean = ((3.8840, 1.5261, 1.6286), (0.8423, 1.7607, 0.6602), (1.7635, 1.7372, 0.5968))
-        mean = [tuple(float(v) for v in row) for row in cfg.MODEL.HEAD.DIMENSION_MEAN]
-        ok = ok and len(mean) == 3 and all(abs(a - b) < 1e-6 for ra, rb in zip(mean, built_in_mean) for a, b in zip(ra, rb))
-        ok = ok and [float(v) for v in cfg.MODEL.HEAD.DEPTH_RANGE] == [0.1, 100.0]
-        if not ok:
-            raise NotImplementedError("the HIP decode kernel implements the runs/monoflex.yaml decode "
-                                      "(output_depth soft / hard / mean / direct / keypoints_* / oracle, inv_sigmoid depth in [0.1, 100], exp dims with the KITTI "
-                                      "DIMENSION_MEAN, multi-bin orientation)")
+        s = self.decode_settings = L.head_decode_settings(cfg)      # the same reading of the config as Loss_Computation's
+        refused = []
+        if key2channel.keys != want or key2channel.channels != [4, 2, 20, 3, 3, 8, 8, 1, 1]:
+            refused.append("regression heads other than the nine-key 50-channel layout of runs/monoflex.yaml")
+        if self.output_depth not in L.DEPTH_MODES and self.output_depth != 'oracle':
+            refused.append("OUTPUT_DEPTH %r" % (self.output_depth,))
+        if cfg.INPUT.ORIENTATION != 'multi-bin' or cfg.INPUT.ORIENTATION_BIN_SIZE != 4:
+            refused.append("an orientation other than multi-bin with 4 bins")
+        if s["down_ratio"] != 4:
+            refused.append("DOWN_RATIO != 4")
+        if s["depth_range"] is None:
+            refused.append("DEPTH_RANGE None (the keypoint depths are clamped to it)")
+        if s["depth_mode"] not in L.DEPTH_DECODES:
+            refused.append("DEPTH_MODE %r" % (s["depth_mode"],))
+        if not 1 <= self.num_classes <= 3:
+            refused.append("%d classes (1 to 3)" % self.num_classes)
+        if len(s["dim_mean"]) < self.num_classes or len(s["dim_std"]) < self.num_classes or len(s["dim_mean"]) > 3 or len(s["dim_std"]) > 3:
+            refused.append("DIMENSION_MEAN / DIMENSION_STD with fewer rows than classes (or more than three)")
+        if refused:
+            raise NotImplementedError("the HIP decode kernel does not implement: " + "; ".join(refused))
+        self.decode_cfg = L.decode_cfg(s, self.uncertainty_as_conf)
 
     @staticmethod
     def prepare_targets(targets, device):
@@ -59,26 +67,32 @@ class PostProcessor(nn.Module):
         size = torch.tensor(list(targets[0].size), dtype=torch.int32, device=device)
         return pad.contiguous(), calib.contiguous(), size
 
-    def decode_device(self, hm, pad, calib, size, cls_planar=None):
-        """hm fp32 (B,H,W,64) -> det (B,K,14), topk (B,K,5) [score, flat index, cls, y, x], valid (B,K) int32."""
+    def decode_device(self, hm, pad, calib, size, cls_planar=None, return_unc=False):
+        """hm fp32 (B,H,W,64) -> det (B,K,14), topk (B,K,5) [score, flat index, cls, y, x], valid (B,K) int32
+        [, unc (B,K,2) = estimated_depth_error, uncertainty_conf]."""
         if self.output_depth == 'oracle':
             raise ValueError("output_depth = 'oracle' reads the ground truth of each image: call the module (forward) with the dataset's targets")
         scores, index = ops.decode_topk(hm, 0, self.num_classes, self.max_detection, planar=cls_planar)
         # (`output_depth` is read at every call: engine/inference.py:166 re-assigns it between the passes of `eval_all_depths`)
-        return ops.decode_boxes(hm, REG_OFF, scores, index, calib, pad, size, float(self.det_threshold), depth_mode=self.output_depth)
+        return ops.decode_boxes(hm, REG_OFF, scores, index, calib, pad, size, float(self.det_threshold), depth_mode=self.output_depth,
+                                cfg=self.decode_cfg, return_unc=return_unc)
 
     def forward(self, predictions, targets, features=None, test=False, refine_module=None):
         hm = predictions['hm_nhwc']
         pad, calib, size = self.prepare_targets(targets, hm.device)
         if self.output_depth == 'oracle':
-            det, topk, valid = self.decode_oracle(hm, pad, calib, size, predictions.get('cls_planar'), targets)
+            det, topk, valid, unc = self.decode_oracle(hm, pad, calib, size, predictions.get('cls_planar'), targets)
         else:
-            det, topk, valid = self.decode_device(hm, pad, calib, size, predictions.get('cls_planar'))
+            det, topk, valid, unc = self.decode_device(hm, pad, calib, size, predictions.get('cls_planar'), return_unc=True)
         keep = valid.bool()
         results = [det[b][keep[b]] for b in range(det.shape[0])]          # host sync, as detector_infer.py:106
         vis_scores = [topk[b][keep[b], 0] for b in range(det.shape[0])]
-        eval_utils = {'dis_ious': None, 'depth_errors': None, 'vis_scores': vis_scores[0] if len(results) == 1 else vis_scores,
-                      'topk': topk, 'valid': valid, 'det_all': det}
+        one = lambda rows: rows[0] if len(results) == 1 else rows
+        # detector_infer.py:223-229,234-235: the valid rows' values under UNCERTAINTY_AS_CONFIDENCE, None without it
+        depth_error = one([unc[b][keep[b], 0] for b in range(det.shape[0])]) if self.uncertainty_as_conf else None
+        unc_conf = one([unc[b][keep[b], 1] for b in range(det.shape[0])]) if self.uncertainty_as_conf else None
+        eval_utils = {'dis_ious': None, 'depth_errors': None, 'vis_scores': one(vis_scores), 'uncertainty_conf': unc_conf,
+                      'estimated_depth_error': depth_error, 'topk': topk, 'valid': valid, 'det_all': det}
         visualize_preds = {'heat_map': predictions['cls']}
         result = results[0] if len(results) == 1 else results
         return result, eval_utils, visualize_preds
@@ -95,12 +109,14 @@ class PostProcessor(nn.Module):
         'mean'): five launches of the box kernel on one top-K, and a per-detection choice of row on the host, where the ground truth is.
         (The reference reads targets[0] only -- it evaluates at batch 1; here image b reads targets[b].)"""
         scores, index = ops.decode_topk(hm, 0, self.num_classes, self.max_detection, planar=cls_planar)
-        dec = {m: ops.decode_boxes(hm, REG_OFF, scores, index, calib, pad, size, float(self.det_threshold), depth_mode=m)
+        dec = {m: ops.decode_boxes(hm, REG_OFF, scores, index, calib, pad, size, float(self.det_threshold), depth_mode=m, cfg=self.decode_cfg,
+                                   return_unc=True)
                for m in ('mean',) + self.ORACLE_COLUMNS}
-        det, topk, valid = dec['mean']
+        det, topk, valid, _ = dec['mean']
         rows = {m: d[0].cpu() for m, d in dec.items()}
+        uncs = {m: d[3].cpu() for m, d in dec.items()}
         valid_h = valid.cpu().bool()
-        out = rows['mean'].clone()
+        out, out_unc = rows['mean'].clone(), uncs['mean'].clone()
         for b, t in enumerate(targets):
             mask = torch.as_tensor(t.get_field('reg_mask')).bool().cpu()
             gt_cls = torch.as_tensor(t.get_field('cls_ids')).cpu()[mask]
@@ -117,8 +133,9 @@ class PostProcessor(nn.Module):
                 if _box_iou(box.numpy(), gt_box[near].numpy()) < 0.5:            # (a 0 / 0 overlap is not "< 0.5": such a pair counts as met, :268-270)
                     continue
                 est = torch.stack([rows[m][b, i, 11] for m in self.ORACLE_COLUMNS])     # row[11] = location z = the depth that decode used
-                out[b, i] = rows[self.ORACLE_COLUMNS[int(torch.argmin(torch.abs(est - gt_depth[near])))]][b, i]
-        return out.to(det.device), topk, valid
+                chosen = self.ORACLE_COLUMNS[int(torch.argmin(torch.abs(est - gt_depth[near])))]
+                out[b, i], out_unc[b, i] = rows[chosen][b, i], uncs[chosen][b, i]
+        return out.to(det.device), topk, valid, out_unc.to(det.device)
 
 
 def _box_iou(a, b):

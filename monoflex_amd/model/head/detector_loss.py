@@ -71,13 +71,15 @@ class Loss_Computation:
                 or self.corner_loss_depth not in ('soft_combine', 'hard_combine', 'direct', 'keypoint_mean'):
             raise NotImplementedError("Loss_Computation is built for the head/loss set of runs/monoflex.yaml")
         # Anno_Encoder constants (anno_encoder.py:11-48)
-        self.depth_mode, self.depth_range = H.DEPTH_MODE, H.DEPTH_RANGE
-        self.depth_ref = tuple(H.DEPTH_REFERENCE)
-        self.dim_mean = torch.as_tensor(H.DIMENSION_MEAN, dtype=torch.float32)
-        self.dim_std = torch.as_tensor(H.DIMENSION_STD, dtype=torch.float32)
-        self.dim_modes = list(H.DIMENSION_REG)
-        self.down_ratio = cfg.MODEL.BACKBONE.DOWN_RATIO
-        self.EPS = 1e-3
+        from ... import lib as L
+        s = self.decode_settings = L.head_decode_settings(cfg)      # one reading of the config for this evaluator and the post-processor's decode
+        self.depth_mode, self.depth_range = s["depth_mode"], s["depth_range"]
+        self.depth_ref = s["depth_ref"]
+        self.dim_mean = torch.as_tensor(s["dim_mean"], dtype=torch.float32)
+        self.dim_std = torch.as_tensor(s["dim_std"], dtype=torch.float32)
+        self.dim_modes = s["dim_modes"]
+        self.down_ratio = s["down_ratio"]
+        self.EPS = s["eps"]
         self.log_as_float = True          # reference returns python floats in log_loss_dict; False keeps 0-d tensors
         self.fused_object_loss = True     # CUDA maps: the regression terms run as ONE kernel (csrc/object_loss_math.h); False = tensor ops
         self._obj_cfg = None
@@ -145,18 +147,12 @@ class Loss_Computation:
                  'keypoint_depth_loss', 'weighted_avg_depth_loss')
         for i, n in enumerate(names):
             c.w[i] = float(W.get(n, 0.0))
-        for i, v in enumerate(self.dim_mean.flatten().tolist()):
-            c.dim_mean[i] = v
-        for i, v in enumerate(self.dim_std.flatten().tolist()):
-            c.dim_std[i] = v
+        c.depth_mode = L.fill_decode_settings(c, self.decode_settings)     # the fields mfx_decode_cfg has too, written by the same code
         for i, v in enumerate(self.dim_weight.flatten().tolist()):
             c.dim_weight[i] = v
-        c.depth_ref[0], c.depth_ref[1] = float(self.depth_ref[0]), float(self.depth_ref[1])
-        c.depth_range[0], c.depth_range[1] = float(self.depth_range[0]), float(self.depth_range[1])
         lo, hi = self.uncertainty_range if self.uncertainty_range is not None else (-float('inf'), float('inf'))
-        c.unc_lo, c.unc_hi, c.down_ratio, c.eps = float(lo), float(hi), float(self.down_ratio), float(self.EPS)
-        c.depth_mode = ('exp', 'linear', 'inv_sigmoid').index(self.depth_mode)
-        c.has_depth_range, c.dim_exp, c.dim_use_std = 1, int(self.dim_modes[0] == 'exp'), int(bool(self.dim_modes[2]))
+        c.unc_lo, c.unc_hi = float(lo), float(hi)
+        c.has_depth_range = 1
         c.iou_type = ('giou', 'iou', 'linear_iou').index(self.iou_type)
         c.corner_depth_mode = ('direct', 'keypoint_mean', 'soft_combine', 'hard_combine').index(self.corner_loss_depth)
         c.separate_trunc, c.trunc_log = int(self.separate_trunc_offset), int(self.trunc_offset_loss_type != 'L1')
