@@ -25,6 +25,7 @@ from torch.autograd.function import once_differentiable
 from . import lib as L
 from . import ops
 from .ops import _dt, _ptr, _stream
+from .packing import _pad_channels, operand_geometry
 
 
 def _c(t):
@@ -164,17 +165,6 @@ def _colsum(t):
     return out
 
 
-def _pad_channels(n, dtype):
-    """Output-channel padding: a power of two (>= one 16-byte chunk) so the padded map is a valid conv input."""
-    e = 4 if dtype == torch.float32 else 8
-    if n >= 64:
-        return (n + 63) // 64 * 64
-    p = e
-    while p < n:
-        p *= 2
-    return p
-
-
 class _PackRegistry:
     """Persistent packed copies of the conv parameters (forward operand, data-gradient operand) with the parameter version they
     were packed from.  A parameter changes once per optimisation step, so `pack_all_weights()` at the top of a step re-packs
@@ -201,12 +191,10 @@ class _PackRegistry:
             E = 4 if dtype == torch.float32 else 8
             if (ck & (ck - 1) and kh * kw > 1) or ck < E or ck % E:
                 raise ValueError("conv operand: channels per tap must be a power of two >= %d (any multiple of %d for 1x1), got %d" % (E, E, ck))
-            kr = 8 * E if kh * kw * ck >= 8 * E else 4 * E      # (a 64-byte K stays 64 bytes: ops.pack_conv)
-            K_pad = (kh * kw * ck + kr - 1) // kr * kr
-            cp = ops.cout_pad(rows)
+            K_pad, cp, fragments = operand_geometry(kh, kw, ck, rows, stride, pad_h, pad_w, E)
             packed = torch.empty((cp, K_pad), dtype=dtype, device=weight.device)
             frag = f16 = None
-            if kh == 3 and kw == 3 and stride in (1, 2) and pad_h == 1 and pad_w == 1:
+            if fragments:
                 if register and dtype == torch.bfloat16 and ck == 64 and cp in (32, 64) and stride == 1 and mode == 0:
                     # a 64-channel DCN layer's operands (_with_f16_fragments): the fragments of all such layers share one arena, so their
                     # IEEE-fp16 copies are ONE cast per step (pack_all) instead of one per operand
@@ -422,10 +410,8 @@ def _pack_weight(weight, dtype, mode, rows, ck, stride, pad_h, pad_w, shift=None
     else:                                                      # a temporary (stacked head weights, a view): nothing to remember
         e = _PACKS.lookup(weight, dtype, mode, rows, ck, stride, pad_h, pad_w, register=False)
         _PACKS.pack_one(e, weight, dtype)
-    p = ops.PackedConv(e["packed"], None, shift, kh, kw, stride, pad_h, pad_w, 1, ck, rows, e["cp"], e["K_pad"], L.ACT_NONE, e["frag"])
-    p.transient = True                                         # rebuilt every step: no derived operand is worth packing behind it (ops.dcn_ps_applies)
-    p.entry = e
-    return p
+    return ops.PackedConv(e["packed"], None, shift, kh, kw, stride, pad_h, pad_w, 1, ck, rows, e["cp"], e["K_pad"], L.ACT_NONE, e["frag"],
+                          transient=True, entry=e)
 
 
 def _with_f16_fragments(p, x):
@@ -437,7 +423,7 @@ def _with_f16_fragments(p, x):
     first-generation gather."""
     if p.w_frag is not None and p.Ck == 64 and p.Cout_pad in (32, 64) and x.shape[0] * x.shape[1] * x.shape[2] >= 65536:      # (32: the module's offset/mask conv, run inside that kernel)
         if p.w.dtype == torch.bfloat16:
-            e = getattr(p, "entry", None)
+            e = p.entry
             if e is not None and e.get("f16") is not None and e["f16_version"] == e["version"] and e["frag"] is p.w_frag:
                 p.w_frag_f16 = e["f16"]                        # this step's batched cast (_PackRegistry.pack_all)
             else:

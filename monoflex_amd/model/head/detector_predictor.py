@@ -121,66 +121,13 @@ class _predictor(nn.Module):
         if key in self._packs:
             return self._packs[key]
         trunks = [self.class_head] + list(self.reg_features)
-        w1, sc, sh = [], [], []
-        for t in trunks:
-            w1.append(t[0].weight.detach().float().permute(0, 2, 3, 1).reshape(self.head_conv, -1))
-            s, b = self._abn_fold(t[1])
-            sc.append(s); sh.append(b)
-        K = w1[0].shape[1]
-        assert K == 576 and self.head_conv == 256
-        E = 4 if dtype in (torch.float32, ops.F16X2) else 8
-        steps = K // (4 * E)
-        nb = len(trunks)
-        dev = w1[0].device
-        w2_scale = None
-        if dtype == ops.F16X2:                                     # weights times a power of two per branch (ops.split_weight_scale), undone by scale1 / w2_scale
-            for i in range(len(w1)):
-                ws = ops.split_weight_scale(w1[i])
-                w1[i], sc[i] = w1[i] * ws, sc[i] / ws
-        # 3x3 weights, fragment-major: [branch][wave wn 4][step][frag j 4][k-group kq 4][row nl 16][E]  (lane = kq*16+nl)
-        W1 = ops.cast_operand(torch.stack(w1, 0).view(nb, 4, 4, 16, steps, 4, E).permute(0, 1, 4, 2, 5, 3, 6).contiguous(), dtype)
-        if dtype == ops.F16X2:
-            W1 = ops.pair_steps(W1, 2)                              # [branch][wn][step pair][hi | lo][j][kq][nl][4]: heads.hip walks K in step pairs
-        w2 = torch.zeros(nb, 32, self.head_conv, device=dev)
-        b2 = torch.zeros(nb, 32, device=dev)
-        ch_off, c_out = [0], [self.num_classes]
-        w2[0, :self.num_classes] = self.class_head[2].weight.detach().float().reshape(self.num_classes, -1)
-        b2[0, :self.num_classes] = self.class_head[2].bias.detach().float()
-        off = REG_OFF
-        for i, heads in enumerate(self.reg_heads):
-            r = 0
-            for h in heads:
-                c = h.weight.shape[0]
-                w2[i + 1, r:r + c] = h.weight.detach().float().reshape(c, -1)
-                b2[i + 1, r:r + c] = h.bias.detach().float()
-                r += c
-            ch_off.append(off); c_out.append(r)
-            off += r
-        assert off <= HM_LD
-        if dtype == ops.F16X2:
-            w2_scale = []
-            for i in range(nb):
-                ws = ops.split_weight_scale(w2[i])
-                w2[i] *= ws
-                w2_scale.append(1.0 / ws)
-        # 1x1 weights, fragment-major with the K order the kernel's accumulators arrive in (heads.hip TrunkPack):
-        #   bf16: [branch][wn][kb 2][of 2][g 4][o_l 16][half 2][q 4], trunk channel n = 64wn + 32kb + 16half + 4g + q
-        #   f32 : [branch][wn][kb 4][of 2][g 4][o_l 16][e 4],          n = 64wn + 16kb + 4g + e
-        if dtype in (torch.float32, ops.F16X2):
-            W2 = ops.cast_operand(w2.view(nb, 2, 16, 4, 4, 4, 4).permute(0, 3, 4, 1, 5, 2, 6).contiguous(), dtype)
-            if dtype == ops.F16X2:
-                W2 = ops.pair_steps(W2, 2)                          # [branch][wn][kb pair][hi | lo][of][g][o_l][4]
-        else:
-            W2 = w2.view(nb, 2, 16, 4, 2, 2, 4, 4).permute(0, 3, 4, 1, 6, 2, 5, 7).contiguous().to(dtype)
-        p = ops.PackedHeads(W1, torch.cat(sc).contiguous(), torch.cat(sh).contiguous(),
-                            W2, b2.contiguous(), K, ch_off, c_out, HM_LD, split=dtype == ops.F16X2, w2_scale=w2_scale)
-        if dtype in (torch.bfloat16, torch.float16):
-            # the same weights for the v_mfma_f32_32x32x16 form (csrc/heads.hip heads_fused32_kernel; option "heads_mfma32"):
-            #   3x3: [branch][wn 4][K-step 36][rb 2][h 2][row 32][8], channel 64 wn + 32 rb + row, k = 16 s + 8 h + e
-            #   1x1: [branch][wn 4][rb 2][t 2][h 2][o 32][a 2][q 4], trunk channel n = 64 wn + 32 rb + 16 t + 8 a + 4 h + q (k-slot e = 4 a + q)
-            w1s = torch.stack(w1, 0)
-            p.w1_32 = w1s.view(nb, 4, 2, 32, 36, 2, 8).permute(0, 1, 4, 2, 5, 3, 6).contiguous().to(dtype)
-            p.w2_32 = w2.view(nb, 32, 4, 2, 2, 2, 2, 4).permute(0, 2, 3, 4, 6, 1, 5, 7).contiguous().to(dtype)
+        lasts = [[self.class_head[2]]] + [list(h) for h in self.reg_heads]
+        c_out = [sum(h.weight.shape[0] for h in heads) for heads in lasts]
+        ch_off = [0] + [REG_OFF + sum(c_out[1:i]) for i in range(1, len(lasts))]      # the class logits, then the regression branches back to back
+        assert ch_off[-1] + c_out[-1] <= HM_LD
+        p = ops.pack_heads([t[0].weight for t in trunks], [self._abn_fold(t[1]) for t in trunks],
+                           [torch.cat([h.weight for h in heads]) for heads in lasts], [torch.cat([h.bias for h in heads]) for heads in lasts],
+                           self.num_classes, ch_off, HM_LD, dtype)
         # edge fusion: trunks of the class branch and of the 3d_offset branch at the border points
         if self.enable_edge_fusion:
             oi = self.offset_index[0]

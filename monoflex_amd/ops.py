@@ -2,18 +2,19 @@
 
 Activations are torch CUDA tensors in physical NHWC layout, shape (B, H, W, C), dtype float32
 (parity mode) or bfloat16 (perf mode).  torch is used for device memory and the current HIP stream
-only; every arithmetic op below runs in libmonoflex_hip.so.  Weight packing (done once per
-`prepare`) uses torch indexing ops -- it is not on the hot path.
+only; every arithmetic op below runs in libmonoflex_hip.so.  The weight layouts these operators
+read are defined in packing.py; its names are re-exported here.
 """
 import ctypes
 import os
-import math
-from dataclasses import dataclass
 from typing import Optional
 
 import torch
 
 from . import lib as L
+from .packing import (F16X2, STEM_PAD_H, STEM_PAD_WL, STEM_PAD_WR, PackedCat, PackedConv, PackedHeads, _elems, _pad_rows_cols, _pow2,       # noqa: F401
+                      _round_up, add_f16_fragments, cast_operand, compute_tag, cout_pad, dcn_pair_fragments, dcn_ps_pack, fold_bn, fragment_major,
+                      pack_cat, pack_conv, pack_heads, pack_stem, pack_upsample, pair_steps, split_chunks, split_halves, split_weight_scale, storage_dtype)
 
 
 def _stream():
@@ -59,68 +60,6 @@ def _dt(dtype):
     raise TypeError("MonoFlex HIP kernels take float32, bfloat16 or float16, got %s" % dtype)
 
 
-# Compute tag of the split-precision mode (include/monoflex_hip.h MFX_F16X2): activations are ordinary float32 tensors, the GEMM
-# kernels (conv2d / cat_conv1x1 / dcn / heads_fused) multiply fp16 (hi, lo) operand pairs.  The tag travels with the PACKED WEIGHTS
-# (`pack_*(…, dtype=F16X2)` -> `.split`), which is what selects the kernel; modules learn it from `compute_tag`.
-F16X2 = "f16x2"
-
-
-def compute_tag(module, dtype):
-    """The pack / kernel tag a module uses for activations of `dtype`: F16X2 when the module was switched to the split-precision
-    mode (KeypointDetector.set_compute_dtype("fp16x2") marks every sub-module) and the activations are fp32."""
-    if dtype == torch.float32 and module.__dict__.get("_mfx_split", False):
-        return F16X2
-    return dtype
-
-
-def storage_dtype(dtype):
-    return torch.float32 if dtype == F16X2 else dtype
-
-
-def _elems(dtype):
-    return 4 if (dtype == torch.float32 or dtype == F16X2) else 8
-
-
-def split_chunks(w):
-    """fp32 tensor (element count a multiple of 4, chunks of 4 consecutive values) -> the same shape, float32-TYPED, every 16-byte
-    chunk holding [4 hi halves | 4 lo halves] of its 4 values: hi = fp16(x), lo = fp16(x - hi) (csrc/common.h f32s_t)."""
-    w = w.detach().float().contiguous()
-    c = w.view(-1, 4)
-    hi = c.half()
-    lo = (c - hi.float()).half()
-    return torch.cat((hi, lo), 1).contiguous().view(torch.float32).view(w.shape)
-
-
-def cast_operand(w, dtype):
-    """Weights as the kernels of compute tag `dtype` read them."""
-    return split_chunks(w) if dtype == F16X2 else w.to(dtype)
-
-
-def pair_steps(x, dim):
-    """Split-precision fragment-major weights for the kernels that walk K in step PAIRS (csrc/heads.hip): `x` is float32-typed with
-    16-byte chunks [hi hi | lo lo] (dwords) in its last axis and the K step on axis `dim`; the result replaces that axis by
-    [pair][hi | lo] and every chunk by [its dwords of step 2p | of step 2p+1]: one 8-element fp16 MFMA operand of hi (lo) halves."""
-    sh = list(x.shape)
-    dim = dim % len(sh)
-    assert sh[-1] == 4 and sh[dim] % 2 == 0
-    lead, mid = sh[:dim], sh[dim + 1:-1]
-    nl, nm = len(lead), len(mid)
-    v = x.reshape(*lead, sh[dim] // 2, 2, *mid, 2, 2)                  # [.., pair, step in pair, mid.., hi/lo, dword]
-    perm = list(range(nl)) + [nl, nl + 2 + nm] + [nl + 2 + i for i in range(nm)] + [nl + 1, nl + 3 + nm]
-    return v.permute(*perm).contiguous().view(*lead, sh[dim] // 2, 2, *mid, 4)
-
-
-def split_weight_scale(w):
-    """Power of two s (python float) that brings max |w| * s into [2^11, 2^12): the lo halves of the scaled weights are then normal
-    fp16 numbers down to |w| = 2^-14 of the largest one (unscaled, every lo half of a |w| < 0.25 weight is an fp16 SUBNORMAL, i.e.
-    carries a 3e-8 absolute error -- ~1e-6 relative on DLA-34's weights, the largest error term of the split mode).  The kernels'
-    epilogues undo it exactly: pack_* fold 1/s into the per-channel `scale`."""
-    m = float(w.detach().abs().max())
-    if not (m > 0.0) or not math.isfinite(m):
-        return 1.0
-    return 2.0 ** (11 - math.floor(math.log2(m)))
-
-
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -137,145 +76,6 @@ def _need_cuda(*ts):
             dev = t.device
         elif t.device != dev:
             raise RuntimeError("MonoFlex HIP operator: operands on different devices (%s and %s)" % (dev, t.device))
-
-
-def _pow2(v):
-    return v > 0 and (v & (v - 1)) == 0
-
-
-def _round_up(v, m):
-    return (v + m - 1) // m * m
-
-
-def cout_pad(c):
-    return 16 if c <= 16 else 32 if c <= 32 else _round_up(c, 64)
-
-
-# --------------------------------------------------------------------------------------------
-# packed parameter containers
-# --------------------------------------------------------------------------------------------
-@dataclass
-class PackedConv:
-    w: torch.Tensor                 # [Cout_pad][K_pad]
-    scale: Optional[torch.Tensor]   # fp32 [Cout_pad]
-    shift: Optional[torch.Tensor]
-    kh: int
-    kw: int
-    stride: int
-    pad_h: int
-    pad_w: int
-    dil_w: int
-    Ck: int
-    Cout: int
-    Cout_pad: int
-    K_pad: int
-    act: int
-    w_frag: Optional[torch.Tensor] = None   # fragment-major copy for the LDS-halo kernel (3x3 / stride 1)
-    w_frag_f16: Optional[torch.Tensor] = None   # same, IEEE fp16 (DCN LDS-patch kernel, bf16 mode)
-    w_frag_pair: Optional[torch.Tensor] = None  # split precision: w_frag with its K steps paired (pair_steps; mfx_conv_desc.w_frag_pair)
-    w_pair_f16: Optional[torch.Tensor] = None   # IEEE fp16, tap-pair K order of the fourth-generation DCN kernel (dcn_pair_fragments; mfx_dcn_desc.w_pair_f16)
-    ps: Optional["PackedConv"] = None           # DCN as project-then-sample: the same weights as ONE 1x1 conv C -> 9*Cout (rows (tap, n)); built on first use (dcn_ps_pack)
-    split: bool = False                     # split-precision operands (F16X2): fp32 activations, MFX_F16X2 kernels
-
-
-def fragment_major(w2d, dtype):
-    """[Cout_pad][K_pad] -> [Cout_pad/16][K_pad/(4E)][4 kq][16 n][E]: one MFMA weight fragment (16 rows x 64 bytes of K)
-    per contiguous KiB, lane (kq*16 + n) owning 16 bytes."""
-    E = _elems(dtype)
-    N, K = w2d.shape
-    assert N % 16 == 0 and K % (4 * E) == 0
-    return w2d.view(N // 16, 16, K // (4 * E), 4, E).permute(0, 2, 3, 1, 4).contiguous()
-
-
-def fold_bn(bn, conv_bias=None, cout_padded=None):
-    """Eval-mode BatchNorm as y = x*scale + shift (a preceding conv bias folded in)."""
-    scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-    shift = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
-    if conv_bias is not None:
-        shift = shift + conv_bias.detach().float() * scale
-    if cout_padded is not None and cout_padded > scale.numel():
-        padn = cout_padded - scale.numel()
-        scale = torch.cat((scale, scale.new_ones(padn)))
-        shift = torch.cat((shift, shift.new_zeros(padn)))
-    return scale.contiguous(), shift.contiguous()
-
-
-def _pad_rows_cols(w2d, rows, cols):
-    out = w2d.new_zeros(rows, cols)
-    out[:w2d.shape[0], :w2d.shape[1]] = w2d
-    return out
-
-
-def pack_conv(weight, dtype, scale=None, shift=None, stride=1, pad=0, act=L.ACT_NONE, cout=None):
-    """weight (Cout,Cin,kh,kw) -> K-contiguous [Cout_pad][K_pad], K = (tap, channel)."""
-    Cout, Cin, kh, kw = weight.shape
-    if not _pow2(Cin) or Cin < _elems(dtype):
-        raise ValueError("pack_conv: Cin must be a power of two >= %d (got %d)" % (_elems(dtype), Cin))
-    K = kh * kw * Cin
-    # 128 bytes of K lets the kernel run 64- or 128-byte k-iterations; a K of 64 bytes (the 32 -> 64 1x1 "project" conv of DLA level 2 in 16-bit modes) stays at
-    # 64: padded to 128 the generic kernel loaded every row twice as wide as it is (19.3 -> 13.4 us at 8 x 96 x 320, tools/pointwise_bench.py)
-    bk = 8 * _elems(dtype) if K >= 8 * _elems(dtype) else 4 * _elems(dtype)
-    K_pad = _round_up(K, bk)
-    cout = Cout if cout is None else cout
-    cp = cout_pad(cout)
-    w2 = weight.detach().float().permute(0, 2, 3, 1).reshape(Cout, K)
-    if dtype == F16X2:
-        ws = split_weight_scale(w2)
-        w2 = w2 * ws
-        scale = (scale.detach().float() if scale is not None else torch.ones(Cout, device=weight.device)) / ws
-    w2 = cast_operand(_pad_rows_cols(w2, cp, K_pad), dtype).contiguous()
-
-    def padv(v, fill):
-        if v is None:
-            return None
-        v = v.detach().float()
-        if v.numel() < cp:
-            v = torch.cat((v, v.new_full((cp - v.numel(),), fill)))
-        return v.contiguous()
-    wf = fragment_major(w2, dtype) if (kh == 3 and kw == 3 and stride in (1, 2) and pad == 1) else None
-    pk = PackedConv(w2, padv(scale, 1.0), padv(shift, 0.0), kh, kw, stride, pad, pad, 1, Cin, cout, cp, K_pad, act, wf, split=dtype == F16X2)
-    if wf is not None and dtype == F16X2 and Cin >= 32:
-        pk.w_frag_pair = pair_steps(wf, 1)
-    return pk
-
-
-# stem geometry: zero-padded NHWC4 image, 3 columns left / 5 right, 3 rows top/bottom
-STEM_PAD_H, STEM_PAD_WL, STEM_PAD_WR = 3, 3, 5
-
-
-def pack_stem(weight, dtype, scale, shift, act=L.ACT_RELU):
-    """7x7/s1/p3 conv on 3 channels (dla_dcn.py:268-272) over the padded NHWC4 image.
-    bf16: a 16-byte chunk is 2 adjacent pixels x 4 ch -> 7 x 4 'super taps' of 8 elements, dil_w = 2.
-    f32 : a chunk is 1 pixel x 4 ch -> 7 x 7 taps of 4 elements."""
-    Cout = weight.shape[0]
-    w = weight.detach().float()
-    w4 = torch.cat((w, w.new_zeros(Cout, 1, 7, 7)), dim=1)              # (Cout,4,7,7)
-    if dtype == F16X2 and Cout == 16:
-        # split precision, dedicated kernel (csrc/stem.hip stem_conv7x7_split_kernel): the fp16 super-tap matrix twice -- hi halves, lo halves
-        w8 = torch.cat((w4, w4.new_zeros(Cout, 4, 7, 1)), dim=3)
-        wp = w8.permute(0, 2, 3, 1).reshape(Cout, 7, 4, 2, 4).reshape(Cout, 7 * 4 * 8)
-        ws = split_weight_scale(wp)
-        wp = wp * ws
-        hi = wp.half()
-        lo = (wp - hi.float()).half()
-        return PackedConv(torch.cat((hi, lo), 0).contiguous(), (scale.detach().float() / ws).contiguous(), shift.contiguous(), 7, 4, 1, 0, 0, 2, 8, Cout,
-                          cout_pad(Cout), wp.shape[1], act, split=True)
-    if dtype in (torch.bfloat16, torch.float16):
-        w8 = torch.cat((w4, w4.new_zeros(Cout, 4, 7, 1)), dim=3)        # kw 7 -> 8
-        # [n][th][j][u][c] with kw = 2j+u
-        wp = w8.permute(0, 2, 3, 1).reshape(Cout, 7, 4, 2, 4).reshape(Cout, 7 * 4 * 8)
-        kh, kw, Ck, dil = 7, 4, 8, 2
-    else:
-        wp = w4.permute(0, 2, 3, 1).reshape(Cout, 7 * 7 * 4)
-        kh, kw, Ck, dil = 7, 7, 4, 1
-    bk = 8 * _elems(dtype)
-    K_pad = _round_up(wp.shape[1], bk)
-    cp = cout_pad(Cout)
-    if dtype == F16X2:
-        ws = split_weight_scale(wp)
-        wp, scale = wp * ws, scale.detach().float() / ws
-    wp = cast_operand(_pad_rows_cols(wp, cp, K_pad), dtype).contiguous()
-    return PackedConv(wp, scale.contiguous(), shift.contiguous(), kh, kw, 1, 0, 0, dil, Ck, Cout, cp, K_pad, act, split=dtype == F16X2)
 
 
 # --------------------------------------------------------------------------------------------
@@ -330,33 +130,6 @@ def conv2d(x, p: PackedConv, res=None, out_dtype=None, rowmap=None, x_channels=N
 conv2d.last_stats_done = False
 
 
-@dataclass
-class PackedCat:
-    w: torch.Tensor
-    scale: torch.Tensor
-    shift: torch.Tensor
-    Cseg: int
-    Cout: int
-    Cout_pad: int
-    K_pad: int
-    act: int
-    split: bool = False
-
-
-def pack_cat(weight, dtype, scale, shift, src_channels, act=L.ACT_RELU):
-    Cout, Ctot = weight.shape[:2]
-    assert sum(src_channels) == Ctot
-    Cseg = min(src_channels)
-    assert all(c % Cseg == 0 for c in src_channels) and _pow2(Cseg)
-    cp = cout_pad(Cout)
-    w2 = weight.detach().float().reshape(Cout, Ctot)
-    if dtype == F16X2:
-        ws = split_weight_scale(w2)
-        w2, scale = w2 * ws, scale.detach().float() / ws
-    w2 = cast_operand(_pad_rows_cols(w2, cp, Ctot), dtype).contiguous()
-    return PackedCat(w2, scale.contiguous(), shift.contiguous(), Cseg, Cout, cp, Ctot, act, split=dtype == F16X2)
-
-
 @on_tensor_device
 def cat_conv1x1(srcs, p: PackedCat):
     """Root: 1x1 conv over the virtual concat of `srcs` (list of (B,H,W,Ci) tensors)."""
@@ -378,48 +151,6 @@ def cat_conv1x1(srcs, p: PackedCat):
     d.dtype = L.MFX_F16X2 if p.split else _dt(y.dtype)
     L.check(L.load().mfx_cat_conv1x1_nhwc(ctypes.byref(d), _stream()), "mfx_cat_conv1x1_nhwc")
     return y
-
-
-def dcn_pair_fragments(weight, cout_pad):
-    """(Cout, Cin, 3, 3) -> the fourth-generation DCN kernel's fp16 weights (csrc/dcn_lds.hip, mfx_dcn_desc.w_pair_f16): the input channels in slices
-    of 16, five MFMA k-steps (K = 32) per slice, k-step j = taps (2j, 2j + 1) x the slice's 16 channels (the tenth tap is zeros); fragment-major
-    [cout_pad / 16][Cin / 16 * 5][4 kq][16 n][8]: lane (kq, n) holds tap 2j + (kq >> 1), channels 16 s + 8 (kq & 1) .. + 7 of output channel 16 nf + n."""
-    Cout, Cin, kh, kw = weight.shape
-    assert kh == 3 and kw == 3 and Cin % 16 == 0 and cout_pad % 16 == 0
-    w = weight.detach().float().permute(0, 2, 3, 1).reshape(Cout, 9, Cin)
-    wp = w.new_zeros(cout_pad, 10, Cin)
-    wp[:Cout, :9] = w
-    wp = wp.view(cout_pad, 5, 2, Cin // 16, 2, 8).permute(0, 3, 1, 2, 4, 5)      # (n, slice, step, tap parity, channel half, 8)
-    w2d = wp.reshape(cout_pad, (Cin // 16) * 5 * 32).to(torch.float16).contiguous()
-    return fragment_major(w2d, torch.float16)
-
-
-def add_f16_fragments(p: PackedConv, weight):
-    """Attach the fp16 fragment-major weights the DCN LDS-patch kernels multiply with (bf16 / fp16 mode, 3x3/s1/p1; split precision: the (hi, lo) halves
-    of the scaled weights as two consecutive arrays each -- csrc/dcn_lds.hip dcn_lds_split_kernel)."""
-    if p.split and p.kh == 3 and p.kw == 3 and p.Cout_pad == 64 and weight.shape[1] % 32 == 0 and p.K_pad == 9 * weight.shape[1]:
-        Cout, Cin, kh, kw = weight.shape
-        w = weight.detach().float().to(p.w.device)
-        ws = split_weight_scale(w.permute(0, 2, 3, 1).reshape(Cout, -1))        # the scale pack_conv folded into p.scale (same matrix, same maximum)
-        w = w * ws
-        hi = w.half()
-        lo = (w - hi.float()).half()
-        p.w_pair_f16 = torch.cat((dcn_pair_fragments(hi.float(), p.Cout_pad).reshape(-1), dcn_pair_fragments(lo.float(), p.Cout_pad).reshape(-1))).contiguous()
-
-        def frag(h):
-            return fragment_major(_pad_rows_cols(h.float().permute(0, 2, 3, 1).reshape(Cout, -1), p.Cout_pad, p.K_pad).half().contiguous(), torch.float16).reshape(-1)
-        p.w_frag_f16 = torch.cat((frag(hi), frag(lo))).contiguous()
-        return p
-    if p.w_frag is not None and p.w.dtype in (torch.float16, torch.bfloat16) and p.kh == 3 and p.kw == 3 and p.Cout_pad == 64 \
-            and weight.shape[1] % 16 == 0 and not p.split:
-        p.w_pair_f16 = dcn_pair_fragments(weight.to(p.w.device), p.Cout_pad)
-    if p.w_frag is not None and p.w.dtype == torch.float16:
-        p.w_frag_f16 = p.w_frag                                  # fp16 mode: the fragments already are IEEE fp16
-    elif p.w_frag is not None and p.w.dtype == torch.bfloat16:
-        Cout, Cin, kh, kw = weight.shape
-        w2 = _pad_rows_cols(weight.detach().float().permute(0, 2, 3, 1).reshape(Cout, kh * kw * Cin), p.Cout_pad, p.K_pad)
-        p.w_frag_f16 = fragment_major(w2.to(device=p.w.device, dtype=torch.float16).contiguous(), torch.float16)
-    return p
 
 
 def _dcn_desc(x, offmask, p: PackedConv, y, off: Optional[PackedConv] = None, offmask_out=None):
@@ -467,18 +198,9 @@ DCN_PS_MAX_BYTES = [int(os.environ.get("MFX_DCN_PS_MAX_MB", "24")) << 20]
 PROJECT_AS = [os.environ.get("MFX_PROJECT_AS", "1") != "0"]      # the projection on csrc/gemm_as.hip (0: mfx_conv2d_nhwc's 1x1 kernel)
 
 
-def dcn_ps_pack(p: PackedConv):
-    """The DCN weights [Cout][(tap, c)] as a 1x1 conv C -> 9 * Cout whose output row is [(tap, n)] (no scale / shift / activation: those follow the sampling)."""
-    if p.ps is None:
-        C = p.K_pad // 9
-        w = p.w[:p.Cout].view(p.Cout, 9, C).permute(1, 0, 2).reshape(9 * p.Cout, C, 1, 1)
-        p.ps = pack_conv(w, p.w.dtype, None, None, stride=1, pad=0, act=L.ACT_NONE)
-    return p.ps
-
-
 def dcn_ps_applies(x, p: PackedConv):
     B, H, W, C = x.shape
-    if getattr(p, "transient", False):                         # training: the projection operand would be re-packed (six launches) every step
+    if p.transient:                                            # training: the projection operand would be re-packed (six launches) every step
         return False
     return (DCN_PS[0] and x.dtype in (torch.bfloat16, torch.float16) and not p.split and p.kh == 3 and p.kw == 3 and p.stride == 1 and p.pad_h == 1
             and p.dil_w == 1 and p.K_pad == 9 * C and C >= 128 and p.Cout == p.Cout_pad and p.Cout in (64, 128, 256)
@@ -532,12 +254,6 @@ def maxpool2x2(x):
     y = torch.empty((B, H // 2, W // 2, C), dtype=x.dtype, device=x.device)
     L.check(L.load().mfx_maxpool2x2_nhwc(_ptr(x), _ptr(y), B, H, W, C, _dt(x.dtype), _stream()), "mfx_maxpool2x2_nhwc")
     return y
-
-
-def pack_upsample(weight):
-    """(C,1,k,k) depthwise deconv weight -> fp32 [k*k][C]."""
-    C, _, k, _ = weight.shape
-    return weight.detach().float().reshape(C, k * k).t().contiguous()
 
 
 @on_tensor_device
@@ -610,34 +326,16 @@ def f1_fused(images, p_stem: PackedConv, p_l0: PackedConv, p_l1: PackedConv):
     dt = torch.float32 if split else p_stem.w.dtype
     assert C == 3 and (split or dt in (torch.bfloat16, torch.float16)) and p_stem.Cout == 16 and p_l0.Cout == 16 and p_l1.Cout == 32 and p_l1.stride == 2
     assert p_l0.split == split and p_l1.split == split
-    key = "_f1_w160"
     for p in (p_l0, p_l1):                                          # [Cout][160] slice of the K-padded (tap, channel) matrix, cached on the pack
-        if not hasattr(p, key):
+        if p.f1_w160 is None:
             assert p.K_pad >= 160 and p.Ck == 16
-            setattr(p, key, p.w[:, :160].contiguous())
+            p.f1_w160 = p.w[:, :160].contiguous()
     y = torch.empty((B, H // 2, W // 2, 32), dtype=dt, device=images.device)
     L.check(L.load().mfx_f1_fused(_ptr(images), _ptr(p_stem.w), _ptr(p_stem.scale), _ptr(p_stem.shift),
-                                  _ptr(getattr(p_l0, key)), _ptr(p_l0.scale), _ptr(p_l0.shift),
-                                  _ptr(getattr(p_l1, key)), _ptr(p_l1.scale), _ptr(p_l1.shift),
+                                  _ptr(p_l0.f1_w160), _ptr(p_l0.scale), _ptr(p_l0.shift),
+                                  _ptr(p_l1.f1_w160), _ptr(p_l1.scale), _ptr(p_l1.shift),
                                   _ptr(y), B, H, W, p_stem.K_pad, L.MFX_F16X2 if split else _dt(dt), _stream()), "mfx_f1_fused")
     return y
-
-
-@dataclass
-class PackedHeads:
-    w1: torch.Tensor
-    scale1: torch.Tensor
-    shift1: torch.Tensor
-    w2: torch.Tensor
-    bias2: torch.Tensor
-    K_pad: int
-    ch_off: list
-    c_out: list
-    ld_out: int
-    split: bool = False
-    w2_scale: Optional[list] = None          # per branch, multiplies the 1x1 sums before the bias (split precision: 1 / the weights' packing scale)
-    w1_32: Optional[torch.Tensor] = None     # packs of the v_mfma_f32_32x32x16 form of the kernel (16-bit modes; mfx_heads_desc.w1_32 / w2_32)
-    w2_32: Optional[torch.Tensor] = None
 
 
 @on_tensor_device
