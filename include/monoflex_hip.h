@@ -310,6 +310,30 @@ int mfx_edge_scatter_add(float* out, int ld_out, int ch_off, int C, const float*
                          const int32_t* edge_xy, const int32_t* edge_len, int B, int L, int H, int W,
                          float* planar /* optional [B][C][H*W], updated too */, void* stream);
 
+/* The conv chain of the edge fusion in one kernel (detector_predictor.py:111-119,152-158; csrc/edge_chain.hip), 16-bit activations: for the two
+ * fusion branches (0 = class, 1 = 3d_offset) and every sequence position p of every image
+ *   out[branch][b][p][0..3] = W3 . act(BN1d(Conv1d_k3(trunk rows at positions p-1, p, p+1, clamped to 0 .. L-1))) + bias
+ * with trunk row(p) = leaky(ABN(conv3x3(x) at pixel edge_xy[b][p])), both intermediates rounded to the activation type -- what
+ * mfx_conv2d_nhwc computes in five launches (row-map trunk, then Conv1d and 1x1 per branch), bit for bit.  Every position 0 .. L-1 is
+ * computed from its listed pixel (the padding rows too); mfx_edge_scatter_add applies edge_len.  Coordinates are clamped into the map.
+ * Weights are the mfx_conv2d_nhwc matrices [rows][K], K = (tap, channel), fragment-major: [rows / 16][K / 32][4 k-groups][16 rows][8]. */
+typedef struct {
+    const void* x;                 /* feature [B][H][W][64]                                                          */
+    const int32_t* edge_xy;        /* [B][L][2] (x, y)                                                               */
+    const void* w_trunk;           /* [2 x 256][576] 3x3 trunk weights, the class branch's rows first                 */
+    const float* scale_trunk; const float* shift_trunk;   /* [2 x 256] folded ABN                                   */
+    const void* w_conv;            /* [2][256][768] Conv1d weights                                                   */
+    const float* scale_conv; const float* shift_conv;     /* [2][256] folded BN1d (Conv1d bias inside)              */
+    const void* w_out;             /* [2][16][256] 1x1 weights, rows past the branch's channels zero                 */
+    const float* bias_out;         /* [2][16]                                                                        */
+    float* out;                    /* [2][B][L][4] fp32                                                              */
+    int32_t B, H, W, C, L, head_conv, ksize, relu /* ReLU after the BN1d (EDGE_FUSION_RELU) */, dtype;
+} mfx_edge_chain_desc;
+/* MFX_ERR_ARG: null pointer or bad sizes; MFX_ERR_UNSUPPORTED: anything but MFX_BF16 / MFX_F16, C = 64, head_conv = 256, ksize = 3 */
+int mfx_edge_chain(const mfx_edge_chain_desc* d, void* stream);
+/* 1 if mfx_edge_chain takes this configuration and option "edge_chain" is on (the caller then replaces its five conv launches by it) */
+int mfx_edge_chain_applies(const mfx_edge_chain_desc* d);
+
 /* Decode stage 1 (layers/utils.py:39-58,61-77): per (image, class) sigmoid+clamp, 3x3 max NMS, top-K.
  * Class logit of (image b, class c, pixel p) is hmap[b*b_stride + c*c_stride + p*p_stride] (elements): either the
  * NHWC head map (c_stride 1, p_stride ld) or a planar (B,ncls,H*W) copy (c_stride H*W, p_stride 1: coalesced).

@@ -42,6 +42,8 @@
     X(heads_mfma32, 0, MFX_NOLO, MFX_NOHI, "1 = the v_mfma_f32_32x32x16 form of the kernel where the caller supplies its packs (mfx_heads_desc.w1_32 / w2_32)") \
     X(heads_planes, 0, MFX_NOLO, MFX_NOHI, "1 = four k-group planes (no LDS bank conflicts: 48 % -> 11 % of the LDS cycles, LDS-active cycles -42 %), " \
         "0 = one 144-byte record per pixel.  Same kernel time (555 vs 555 us, A/B in one run): not LDS-bound") \
+    X(edge_chain, 1, MFX_NOLO, MFX_NOHI, "1 = the edge fusion's conv chain (trunk, Conv1d, 1x1 of both branches) as one kernel where mfx_edge_chain applies " \
+        "(edge_chain.hip: 16-bit modes, bit-identical output), 0 = five mfx_conv2d_nhwc launches") \
     X(topk_strips, 8, MFX_NOLO, MFX_NOHI, "row strips per (class, image) map when a workspace is supplied; 1 = single-workgroup kernel") \
     X(topk_merge_z, 16, MFX_NOLO, MFX_NOHI, "workgroups per (class, image) map in the merge; values outside 1..64 are an error") \
     X(topk_merge_threads, 512, MFX_NOLO, MFX_NOHI, "their size; must be a multiple of 64 in 64..512 (the merge ranks by whole wavefronts; 512 = its __launch_bounds__)") \
@@ -105,6 +107,7 @@
     X(conv_igemm, "launches of the generic implicit-GEMM kernel (conv_kernels.hip)") \
     X(conv_splitk, "those that ran split-K") \
     X(conv_bn_stats, "convolutions whose epilogue accumulated the BatchNorm statistics") \
+    X(edge_chain, "launches of the edge fusion's one-kernel conv chain (edge_chain.hip)") \
     /* training-side families */ \
     X(wgrad_patch, "weight gradients by the LDS-patch kernel (wgrad_tr.hip)") \
     X(wgrad_tr, "weight gradients by the transposed-read kernel (wgrad_tr.hip)") \

@@ -55,6 +55,12 @@ class HeadsDesc(ctypes.Structure):
                 ("w1_32", c_void_p), ("w2_32", c_void_p)]
 
 
+class EdgeChainDesc(ctypes.Structure):                          # mfx_edge_chain_desc
+    _fields_ = [(n, c_void_p) for n in ("x", "edge_xy", "w_trunk", "scale_trunk", "shift_trunk", "w_conv", "scale_conv", "shift_conv",
+                                        "w_out", "bias_out", "out")] + \
+        [(n, c_int) for n in ("B", "H", "W", "C", "L", "head_conv", "ksize", "relu", "dtype")]
+
+
 class KittiDesc(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in (
         "records", "n_obj", "P", "img_wh", "flip", "hm", "cls_ids", "target_centers", "keypoints", "keypoints_depth_mask",
@@ -153,6 +159,8 @@ SYMBOLS = {
     "mfx_heads_fused": (_I, [ctypes.POINTER(HeadsDesc), _P]),
     "mfx_dcn_fuses_offset_conv": (_I, [ctypes.POINTER(DcnDesc)]),
     "mfx_edge_scatter_add": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "mfx_edge_chain": (_I, [ctypes.POINTER(EdgeChainDesc), _P]),
+    "mfx_edge_chain_applies": (_I, [ctypes.POINTER(EdgeChainDesc)]),
     "mfx_decode_topk_workspace_bytes": (_S, [_I, _I, _I]),
     "mfx_decode_topk": (_I, [_P, ctypes.c_long, ctypes.c_long, ctypes.c_long, _I, _I, _I, _I, _I, _P, _P, _P, _S, _P]),
     "mfx_conv_wgrad_nhwc": (_I, [_P, _P, _P] + [_I] * 15 + [_P]),

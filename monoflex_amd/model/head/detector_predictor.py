@@ -146,6 +146,7 @@ class _predictor(nn.Module):
                                     act=L.ACT_RELU if self.edge_fusion_relu else L.ACT_NONE)
                 pk2 = ops.pack_conv(c3.weight.detach().unsqueeze(2), dtype, None, c3.bias, stride=1, pad=0, act=L.ACT_NONE, cout=4)
                 p.edge_branches.append((pk1, pk2, cout, choff))
+            p.edge_chain = ops.pack_edge_chain(p.edge_trunk, p.edge_branches)      # 16-bit modes: the same operands for the one-kernel chain
         self._packs[key] = p
         return p
 
@@ -163,6 +164,11 @@ class _predictor(nn.Module):
                 raise ValueError("edge fusion is enabled: targets must carry edge_indices / edge_len")
             B, H, W, _ = features.shape
             Lmax = edge_indices.shape[1]
+            chain = ops.edge_chain(features, edge_indices, p.edge_chain) if p.edge_chain is not None else None
+            if chain is not None:                                       # trunk + Conv1d + 1x1 of both branches in one kernel (reads edge_indices: no row map)
+                for bi, (_, _, cout, choff) in enumerate(p.edge_branches):
+                    ops.edge_scatter_add(hm, choff, cout, chain[bi], edge_indices, edge_lens, planar=planar if choff == 0 else None)
+                return hm
             rowmap = edge_rowmap if edge_rowmap is not None else make_edge_rowmap(edge_indices, H, W)
             trunk = ops.conv2d(features, p.edge_trunk, rowmap=rowmap)   # (B*(L+2), 512)
             trunk = trunk.view(B, 1, Lmax + 2, 2 * self.head_conv)

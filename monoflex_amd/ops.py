@@ -12,9 +12,10 @@ from typing import Optional
 import torch
 
 from . import lib as L
-from .packing import (F16X2, STEM_PAD_H, STEM_PAD_WL, STEM_PAD_WR, PackedCat, PackedConv, PackedHeads, _elems, _pad_rows_cols, _pow2,       # noqa: F401
+from .packing import (F16X2, STEM_PAD_H, STEM_PAD_WL, STEM_PAD_WR, PackedCat, PackedConv, PackedEdgeChain, PackedHeads, _elems, _pad_rows_cols, _pow2,       # noqa: F401
                       _round_up, add_f16_fragments, cast_operand, compute_tag, cout_pad, dcn_pair_fragments, dcn_ps_pack, fold_bn, fragment_major,
-                      pack_cat, pack_conv, pack_heads, pack_stem, pack_upsample, pair_steps, split_chunks, split_halves, split_weight_scale, storage_dtype)
+                      pack_cat, pack_conv, pack_edge_chain, pack_heads, pack_stem, pack_upsample, pair_steps, split_chunks, split_halves, split_weight_scale,
+                      storage_dtype)
 
 
 def _stream():
@@ -359,6 +360,31 @@ def heads_fused(x, p: PackedHeads, planar_classes=0):
         d.w2_scale[i] = p.w2_scale[i] if p.w2_scale is not None else 1.0
     L.check(L.load().mfx_heads_fused(ctypes.byref(d), _stream()), "mfx_heads_fused")
     return out, planar
+
+
+@on_tensor_device
+def edge_chain(x, edge_xy, p: PackedEdgeChain):
+    """The edge fusion's conv chain in one kernel: x (B,H,W,64) 16-bit, edge_xy int32 (B,L,2) -> fp32 (2,B,L,4), [0] the class branch's and [1]
+    the 3d_offset branch's Conv1d output at every sequence position (what edge_scatter_add adds to the head map).  None where the library keeps
+    the five conv launches (option "edge_chain" off, or not a 16-bit map): the caller runs those."""
+    _need_cuda(x, edge_xy)
+    B, H, W, C = x.shape
+    Lmax = edge_xy.shape[1]
+    if edge_xy.dtype != torch.int32 or not edge_xy.is_contiguous() or not x.is_contiguous() or x.dtype != p.w_trunk.dtype:
+        return None
+    d = L.EdgeChainDesc()
+    d.x, d.edge_xy = x.data_ptr(), edge_xy.data_ptr()
+    d.w_trunk, d.scale_trunk, d.shift_trunk = p.w_trunk.data_ptr(), p.scale_trunk.data_ptr(), p.shift_trunk.data_ptr()
+    d.w_conv, d.scale_conv, d.shift_conv = p.w_conv.data_ptr(), p.scale_conv.data_ptr(), p.shift_conv.data_ptr()
+    d.w_out, d.bias_out = p.w_out.data_ptr(), p.bias_out.data_ptr()
+    d.B, d.H, d.W, d.C, d.L, d.head_conv, d.ksize, d.relu, d.dtype = B, H, W, C, Lmax, 256, 3, int(p.relu), _dt(x.dtype)
+    lib = L.load()
+    if not lib.mfx_edge_chain_applies(ctypes.byref(d)):
+        return None
+    out = torch.empty((2, B, Lmax, 4), dtype=torch.float32, device=x.device)
+    d.out = out.data_ptr()
+    L.check(lib.mfx_edge_chain(ctypes.byref(d), _stream()), "mfx_edge_chain")
+    return out
 
 
 @on_tensor_device

@@ -162,6 +162,21 @@ class PackedHeads:
     w2_32: Optional[torch.Tensor] = None
     edge_trunk: Optional[PackedConv] = None  # edge fusion (detector_predictor._pack): the class and 3d_offset trunks as one conv at the border points
     edge_branches: Optional[list] = None     # ... and per fusion branch (Conv1d k3 pack, Conv1d 1x1 pack, channels, channel offset in the head map)
+    edge_chain: Optional["PackedEdgeChain"] = None   # the same five operands for the one-kernel chain (16-bit modes; pack_edge_chain)
+
+
+@dataclass
+class PackedEdgeChain:
+    """mfx_edge_chain's operands (csrc/edge_chain.hip): fragment-major weights, branch 0 = class, 1 = 3d_offset."""
+    w_trunk: torch.Tensor       # [2 x 16][18][4][16][8]
+    scale_trunk: torch.Tensor   # fp32 [2 x 256]
+    shift_trunk: torch.Tensor
+    w_conv: torch.Tensor        # [2][16][24][4][16][8]
+    scale_conv: torch.Tensor    # fp32 [2][256]
+    shift_conv: torch.Tensor
+    w_out: torch.Tensor         # [2][1][8][4][16][8]
+    bias_out: torch.Tensor      # fp32 [2][16]
+    relu: bool
 
 
 def fragment_major(w2d, dtype):
@@ -171,6 +186,28 @@ def fragment_major(w2d, dtype):
     N, K = w2d.shape
     assert N % 16 == 0 and K % (4 * E) == 0
     return w2d.view(N // 16, 16, K // (4 * E), 4, E).permute(0, 2, 3, 1, 4).contiguous()
+
+
+def pack_edge_chain(trunk: PackedConv, branches):
+    """The edge fusion's five conv operands (detector_predictor._pack: the row-map trunk of both branches, per branch the Conv1d k3 and the 1x1
+    pack) as the one-kernel chain reads them: the SAME [rows][K] matrices, K = (tap, channel), fragment-major, so that both forms multiply the
+    same numbers in the same K order.  16-bit packs of the 64 -> 256 trunk, a k = 3 Conv1d and at most 4 output channels; None otherwise."""
+    dtype = trunk.w.dtype
+    if trunk.split or dtype not in (torch.bfloat16, torch.float16) or len(branches) != 2:
+        return None
+    if (trunk.kh, trunk.kw, trunk.Ck, trunk.Cout, trunk.K_pad) != (3, 3, 64, 512, 576):
+        return None
+    for pk1, pk2, cout, _ in branches:
+        if (pk1.kh, pk1.kw, pk1.Ck, pk1.Cout, pk1.K_pad) != (1, 3, 256, 256, 768) or pk1.act not in (ACT_NONE, ACT_RELU) or pk1.act != branches[0][0].act:
+            return None
+        if (pk2.kh, pk2.kw, pk2.Ck, pk2.Cout_pad, pk2.K_pad) != (1, 1, 256, 16, 256) or cout > 4 or pk2.scale is not None or pk2.act != ACT_NONE:
+            return None
+    return PackedEdgeChain(fragment_major(trunk.w, dtype), trunk.scale, trunk.shift,
+                           torch.stack([fragment_major(pk1.w, dtype) for pk1, _, _, _ in branches]).contiguous(),
+                           torch.stack([pk1.scale for pk1, _, _, _ in branches]).contiguous(),
+                           torch.stack([pk1.shift for pk1, _, _, _ in branches]).contiguous(),
+                           torch.stack([fragment_major(pk2.w, dtype) for _, pk2, _, _ in branches]).contiguous(),
+                           torch.stack([pk2.shift for _, pk2, _, _ in branches]).contiguous(), branches[0][0].act == ACT_RELU)
 
 
 def fold_bn(bn, conv_bias=None):
