@@ -383,6 +383,22 @@ int mfx_decode_boxes_cfg(const float* hmap, int ld, int reg_off, const float* sc
                          int ncls, int B, int H, int W, int K, const float* calib, const int32_t* pad,
                          const int32_t* img_size, float threshold, const mfx_decode_cfg* cfg, float* det, float* topk, int32_t* valid,
                          float* unc, void* stream);
+/* The same for any head set the reference accepts (MODEL.HEAD.REGRESSION_HEADS / REGRESSION_CHANNELS): `heads` gives the first channel of
+ * 2d_dim, 3d_offset, corner_offset, corner_uncertainty, 3d_dim, ori_cls, ori_offset, depth, depth_uncertainty within the reg_width (<= 50)
+ * regression channels at [reg_off, reg_off + reg_width); -1 marks an absent optional key (corner_offset, corner_uncertainty -- only with
+ * corner_offset --, depth_uncertainty).  mfx_decode_boxes_cfg is this entry with the runs/monoflex.yaml layout.  As detector_infer.py:148-204:
+ * keypoints_* need corner_offset; soft / hard / mean need corner_offset and corner_uncertainty and, without depth_uncertainty, combine the three
+ * keypoint depths alone; an output_depth the set cannot serve is MFX_ERR_ARG.  Where the chosen estimate has no uncertainty head (direct
+ * without depth_uncertainty, keypoints_* without corner_uncertainty) the reference's estimated_depth_error is None: unc is 0 and
+ * uncertainty_as_conf has no effect. */
+typedef struct mfx_head_layout {
+    int ch[9];
+    int reg_width;
+} mfx_head_layout;
+int mfx_decode_boxes_heads(const float* hmap, int ld, int reg_off, const float* scores, const int32_t* index,
+                           int ncls, int B, int H, int W, int K, const float* calib, const int32_t* pad,
+                           const int32_t* img_size, float threshold, const mfx_decode_cfg* cfg, const mfx_head_layout* heads,
+                           float* det, float* topk, int32_t* valid, float* unc, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (3) training path (reference: autograd over nn.Conv2d / BatchNorm2d / MaxPool2d / ConvTranspose2d and
@@ -557,7 +573,7 @@ int mfx_focal_loss(const float* logits_nhwc, const float* heat_nchw, int B, int 
  * object row; lane c carries d/d(channel c) through the expression in forward mode, so the value of every term and its
  * gradient row come out of the same launch.
  *   rows  fp32 [N][MFX_OBJ_ROW]: one row per (image, object slot), N = B * MAX_OBJECTS (layout: csrc/object_loss_math.h R_*)
- *   reg   fp32 NHWC map, pixel stride `ld`, the 50 regression channels at [ch_off, ch_off + 50) of every pixel
+ *   reg   fp32 NHWC map, pixel stride `ld`, the R = cfg.reg_width regression channels at [ch_off, ch_off + R) of every pixel
  *   vals  fp32 [MFX_OBJ_VALUES] (overwritten): [0, MFX_OBJ_TERMS) the weighted loss terms bbox, depth, offset, trunc_offset, orien,
  *         dims, corner, keypoint, keypoint_depth, weighted_avg_depth; then the logged means (2D_IoU, depth_loss, keypoint_depth_loss,
  *         depth / center / 02 / 13 / lower / hard / soft / mean MAE, and in slot 21 the 3D_IoU: the mean over the valid rows of the rotated
@@ -565,7 +581,12 @@ int mfx_focal_loss(const float* logits_nhwc, const float* heat_nchw, int B, int 
  *   G     fp32 [N][MFX_OBJ_TERMS][64] (overwritten): d(term)/d(channel) at the object's pixel
  * mfx_object_loss_backward ADDS sum_t gout[t] * G[n][t][c] into dreg (same geometry as reg; the caller zero-fills it): objects
  * sharing a centre pixel accumulate, as the gather's backward does.
- * B = 0 selects the GATHERED form: reg / dreg are [N][ld] tables, row n belonging to object row n (mfx_head_sparse_fwd's output). */
+ * B = 0 selects the GATHERED form: reg / dreg are [N][ld] tables, row n belonging to object row n (mfx_head_sparse_fwd's output).
+ * Head sets: depth_uncertainty, corner_offset and corner_uncertainty are optional keys; ch[i] == -1 marks an absent one (its terms and
+ * logged values are 0, the rest follows the reference's branches for the missing head: plain L1 depth, three-way combination of the keypoint
+ * depths, keypoint depths without exp(-u)).  MFX_ERR_ARG: a required key absent, a key reaching past reg_width, corner_uncertainty without
+ * corner_offset, a corner_depth_mode the set cannot serve (keypoint_mean needs corner_offset; soft / hard combine need all nine keys).
+ * mfx_object_loss_backward is mfx_object_loss_backward_width with reg_width = 50; only channels [ch_off, ch_off + reg_width) are written. */
 #define MFX_OBJ_ROW 72
 #define MFX_OBJ_TERMS 10
 #define MFX_OBJ_VALUES 24
@@ -580,12 +601,15 @@ typedef struct mfx_object_loss_cfg {
     int corner_depth_mode;                /* 0 direct, 1 keypoint_mean, 2 soft_combine, 3 hard_combine */
     int separate_trunc, trunc_log, modify_invalid;
     int ch[9];                            /* first channel of 2d_dim, 3d_offset, corner_offset, corner_uncertainty, 3d_dim, ori_cls,
-                                             ori_offset, depth, depth_uncertainty within the 50 */
+                                             ori_offset, depth, depth_uncertainty within the row; -1 = absent (optional keys only) */
+    int reg_width;                        /* R: regression channels per row, every present key inside [0, R); 0 = 50 (the full set) */
 } mfx_object_loss_cfg;
 int mfx_object_loss(const float* reg_nhwc, int B, int H, int W, int ld, int ch_off, const float* rows, int N,
                     const mfx_object_loss_cfg* cfg, float* vals, float* G, void* stream);
 int mfx_object_loss_backward(const float* G, const float* gout_terms, const float* rows, int N, int B, int H, int W,
                              float* dreg_nhwc, int ld, int ch_off, void* stream);
+int mfx_object_loss_backward_width(const float* G, const float* gout_terms, const float* rows, int N, int B, int H, int W,
+                                   float* dreg_nhwc, int ld, int ch_off, int reg_width, void* stream);
 
 /* Rotated 3D box IoU of N matched box pairs (csrc/box3d_iou.hip; reference get_iou_3d, model/layers/iou_loss.py:99-136, the logged
  * `3D_IoU` of model/head/detector_loss.py:333,436 -- there a host loop over shapely polygons).  Upright boxes rotated about Y:

@@ -1071,7 +1071,7 @@ class FocalLossFn(Function):
 @_device_guarded
 class ObjectLossFn(Function):
     """The nine per-object regression terms (detector_loss.py:116-482) in one launch (csrc/object_loss_math.h): fp32 NHWC map
-    with the 50 regression channels at [ch_off, ch_off+50) of each pixel + the packed target rows -> (terms[10], logged[14]);
+    with the R = cfg.reg_width (0: 50) regression channels at [ch_off, ch_off+R) of each pixel + the packed target rows -> (terms[10], logged[14]);
     the gradient row of every term is produced by the same launch (forward-mode tangents, one lane per channel), backward is a
     scatter-add of sum_t gout[t] * G[n][t][:] into a zero map."""
 
@@ -1093,7 +1093,7 @@ class ObjectLossFn(Function):
         L.check(L.load().mfx_object_loss(_ptr(reg), B, H, W, ld, ch_off, _ptr(rows), N, ctypes.byref(cfg), _ptr(vals), _ptr(G), _stream()),
                 "mfx_object_loss")
         ctx.save_for_backward(G, rows)
-        ctx.geom = (B, H, W, ld, ch_off)
+        ctx.geom = (B, H, W, ld, ch_off, cfg.reg_width or 50)
         terms, logged = vals[:L.OBJ_TERMS], vals[L.OBJ_TERMS:]
         ctx.mark_non_differentiable(logged)
         return terms, logged
@@ -1102,11 +1102,11 @@ class ObjectLossFn(Function):
     @once_differentiable
     def backward(ctx, g_terms, g_logged):
         G, rows = ctx.saved_tensors
-        B, H, W, ld, ch_off = ctx.geom
+        B, H, W, ld, ch_off, R = ctx.geom
         dreg = torch.zeros((W, ld) if B == 0 else (B, H, W, ld), dtype=torch.float32, device=G.device)
         g = _c(g_terms.float())
-        L.check(L.load().mfx_object_loss_backward(_ptr(G), _ptr(g), _ptr(rows), rows.shape[0], B, H, W, _ptr(dreg), ld, ch_off, _stream()),
-                "mfx_object_loss_backward")
+        L.check(L.load().mfx_object_loss_backward_width(_ptr(G), _ptr(g), _ptr(rows), rows.shape[0], B, H, W, _ptr(dreg), ld, ch_off, R, _stream()),
+                "mfx_object_loss_backward_width")
         return dreg, None, None, None
 
 

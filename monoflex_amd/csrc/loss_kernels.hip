@@ -122,11 +122,11 @@ __global__ __launch_bounds__(64) void object_loss_kernel(const float* __restrict
 
 __global__ __launch_bounds__(64) void object_loss_bwd_kernel(const float* __restrict__ G, const float* __restrict__ gout,
                                                              const float* __restrict__ rows, int N, int B, int H, int W,
-                                                             float* __restrict__ dreg, int ld, int ch_off) {
+                                                             float* __restrict__ dreg, int ld, int ch_off, int R) {
     const int lane = threadIdx.x;
     for (int n = blockIdx.x; n < N; n += gridDim.x) {       // (deterministic mode: one wave, objects that share a pixel add in order)
         const float* t = rows + (size_t)n * ROW;
-        if (t[R_VALID] == 0.f || lane >= 50) continue;
+        if (t[R_VALID] == 0.f || lane >= R) continue;          // lanes >= R carry nothing: the row ends at channel R
         float g = 0.f;
 #pragma unroll
         for (int k = 0; k < NTERM; ++k) g += gout[k] * G[((size_t)n * NTERM + k) * 64 + lane];
@@ -140,9 +140,9 @@ __global__ __launch_bounds__(64) void object_loss_bwd_kernel(const float* __rest
 extern "C" int mfx_object_loss(const float* reg_nhwc, int B, int H, int W, int ld, int ch_off, const float* rows, int N,
                                const mfx_object_loss_cfg* cfg, float* vals, float* G, void* stream) {
     if (!reg_nhwc || !rows || !cfg || !vals || !G) return mfx_fail(MFX_ERR_ARG, "object_loss: null pointer");
-    if (B < 0 || (B > 0 && (H < 1 || W < 1)) || N < 0 || ch_off < 0 || ch_off + 50 > ld) return mfx_fail(MFX_ERR_ARG, "object_loss: bad sizes");
-    for (int i = 0; i < 9; ++i)
-        if (cfg->ch[i] < 0 || cfg->ch[i] >= 50) return mfx_fail(MFX_ERR_ARG, "object_loss: channel offset outside the 50 regression channels");
+    if (cfg->reg_width < 0 || cfg->reg_width > MAX_REG) return mfx_fail(MFX_ERR_ARG, "object_loss: reg_width must be 0 (the full 50) or 1..50");
+    if (B < 0 || (B > 0 && (H < 1 || W < 1)) || N < 0 || ch_off < 0 || ch_off + reg_width(*cfg) > ld) return mfx_fail(MFX_ERR_ARG, "object_loss: bad sizes");
+    if (const char* why = head_set_error(*cfg)) return mfx_fail(MFX_ERR_ARG, why);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MFX_HIP_CHECK(mfx::zero_async(vals, sizeof(float) * MFX_OBJ_VALUES, st));
     if (N == 0) return MFX_OK;
@@ -153,11 +153,17 @@ extern "C" int mfx_object_loss(const float* reg_nhwc, int B, int H, int W, int l
 
 extern "C" int mfx_object_loss_backward(const float* G, const float* gout_terms, const float* rows, int N, int B, int H, int W,
                                         float* dreg_nhwc, int ld, int ch_off, void* stream) {
+    return mfx_object_loss_backward_width(G, gout_terms, rows, N, B, H, W, dreg_nhwc, ld, ch_off, MAX_REG, stream);
+}
+
+extern "C" int mfx_object_loss_backward_width(const float* G, const float* gout_terms, const float* rows, int N, int B, int H, int W,
+                                              float* dreg_nhwc, int ld, int ch_off, int reg_width, void* stream) {
     if (!G || !gout_terms || !rows || !dreg_nhwc) return mfx_fail(MFX_ERR_ARG, "object_loss_backward: null pointer");
-    if (B < 0 || (B > 0 && (H < 1 || W < 1)) || N < 0 || ch_off < 0 || ch_off + 50 > ld) return mfx_fail(MFX_ERR_ARG, "object_loss_backward: bad sizes");
+    if (reg_width < 1 || reg_width > MAX_REG) return mfx_fail(MFX_ERR_ARG, "object_loss_backward: reg_width must be 1..50");
+    if (B < 0 || (B > 0 && (H < 1 || W < 1)) || N < 0 || ch_off < 0 || ch_off + reg_width > ld) return mfx_fail(MFX_ERR_ARG, "object_loss_backward: bad sizes");
     if (N == 0) return MFX_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(object_loss_bwd_kernel, dim3(g_opt_deterministic ? 1 : N), dim3(64), 0, st, G, gout_terms, rows, N, B, H, W, dreg_nhwc, ld, ch_off);
+    hipLaunchKernelGGL(object_loss_bwd_kernel, dim3(g_opt_deterministic ? 1 : N), dim3(64), 0, st, G, gout_terms, rows, N, B, H, W, dreg_nhwc, ld, ch_off, reg_width);
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }

@@ -1,5 +1,5 @@
-// Per-object regression losses of the detection head and their gradient, as one function of (50 regression channels at the
-// object's centre pixel, the object's target row) -- C ABI mfx_object_loss / mfx_object_loss_backward.
+// Per-object regression losses of the detection head and their gradient, as one function of (the R <= 50 regression channels at
+// the object's centre pixel, the object's target row) -- C ABI mfx_object_loss / mfx_object_loss_backward.
 //
 // Reference: model/head/detector_loss.py:116-482 (prepare_predictions + the nine regression terms + the logged MAEs) with
 // the decoders of model/anno_encoder.py:88-295, model/layers/iou_loss.py:7-49 and data/datasets/kitti_utils.py:350-369.  The
@@ -8,6 +8,11 @@
 // (Dual below), which gives the exact gradient row of every loss term in the same pass -- no hand-derived backward to keep
 // in sync.  Non-differentiable selections (arg max of the orientation bins, `.detach()`ed operands) simply carry a zero tangent.
 // kitti_eval_math.h-style: plain functions, loss_kernels.hip maps lanes onto them, tests/shim compiles them for the host.
+//
+// Head sets (the reference's ablation ladder): three of the nine keys are optional -- depth_uncertainty, corner_offset and
+// corner_uncertainty (only with corner_offset); cfg.ch[i] == -1 marks an absent one.  Its channels are never read, the terms and
+// logged values that need it come out 0, and the rest follows the reference's `if self.depth_with_uncertainty` /
+// `compute_keypoint_corner` / `corner_with_uncertainty` branches (head_set_error below lists what each set can serve).
 #pragma once
 #include <cmath>
 
@@ -36,6 +41,28 @@ enum { T_BBOX = 0, T_DEPTH, T_OFFSET, T_TRUNC_OFFSET, T_ORIEN, T_DIMS, T_CORNER,
 static_assert(V_IOU3D == 21 && V_IOU3D < NVAL, "the logged 3D IoU is value slot 21");
 enum { N_V = 0, N_V2D, N_V_INSIDE, N_TRUNC, N_KMASK, N_KD_VALID, N_KD_INVALID, N_ORI };
 enum { C_2D = 0, C_OFF3D, C_CORNER, C_CORNER_UNC, C_DIM, C_ORI_CLS, C_ORI_OFF, C_DEPTH, C_DEPTH_UNC };
+constexpr int MAX_REG = 50;                                        // the full head set's width; a reduced set is 26..49 wide
+
+// regression width the caller states (cfg.reg_width; 0 = the full 50)
+MFX_HD int reg_width(const mfx_object_loss_cfg& c) { return c.reg_width == 0 ? MAX_REG : c.reg_width; }
+// What is wrong with a head set / corner depth mode, or nullptr: the required keys present and inside the row, corner_uncertainty only
+// next to corner_offset, keypoint_mean only with keypoints, soft / hard combine only with all four depth estimates and their uncertainties.
+inline const char* head_set_error(const mfx_object_loss_cfg& c) {
+    const int R = reg_width(c);
+    const int width[9] = {4, 2, 20, 3, 3, 8, 8, 1, 1};
+    if (R < 1 || R > MAX_REG) return "reg_width outside 1..50";
+    for (int i = 0; i < 9; ++i) {
+        const bool optional = i == C_CORNER || i == C_CORNER_UNC || i == C_DEPTH_UNC;
+        if (c.ch[i] < 0 && !(optional && c.ch[i] == -1)) return "a required regression key is absent (channel start < 0)";
+        if (c.ch[i] >= 0 && c.ch[i] + width[i] > R) return "a regression key's channels reach past the row (channel start + width > reg_width)";
+    }
+    if (c.ch[C_CORNER_UNC] >= 0 && c.ch[C_CORNER] < 0) return "corner_uncertainty without corner_offset";
+    if (c.corner_depth_mode < 0 || c.corner_depth_mode > 3) return "corner_depth_mode outside 0..3";
+    if (c.corner_depth_mode == 1 && c.ch[C_CORNER] < 0) return "corner_depth_mode keypoint_mean needs corner_offset";
+    if (c.corner_depth_mode >= 2 && (c.ch[C_CORNER] < 0 || c.ch[C_CORNER_UNC] < 0 || c.ch[C_DEPTH_UNC] < 0))
+        return "corner_depth_mode soft_combine / hard_combine needs corner_offset, corner_uncertainty and depth_uncertainty";
+    return nullptr;
+}
 
 // ---- forward-mode value/tangent pair ------------------------------------------------------------------------------------------
 struct Dual { float v, d; };
@@ -89,7 +116,7 @@ MFX_HD Vec3 box_corner(int k, Dual cs, Dual sn, const Dual* dims, const Vec3& lo
     return Vec3{cs * x + sn * z + loc.x, y + loc.y, -(sn * x) + cs * z + loc.z};
 }
 
-// One object.  X(ch) returns channel `ch` of the 50 regression channels at the object's pixel as a Dual seeded for this lane;
+// One object.  X(ch) returns channel `ch` of the regression channels at the object's pixel as a Dual seeded for this lane;
 // `t` is the target row, `nrm` the eight batch-wide selection counts.  out[NVAL] ACCUMULATES nothing: it is overwritten with this
 // object's contribution to each loss term (already weighted and divided by its count) and to each logged mean.
 template <typename Reader>
@@ -105,6 +132,7 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
     const float* pad = t + R_PAD;
     const float t_depth = t[R_DEPTH];
     const float inv_v = 1.f / cnt(N_V);
+    const bool has_du = c.ch[C_DEPTH_UNC] >= 0, has_kp = c.ch[C_CORNER] >= 0, has_cu = has_kp && c.ch[C_CORNER_UNC] >= 0;
 
     // ---- 2D box: GIoU / IoU of the four ReLU'ed side distances (iou_loss.py:12-49) ---------------------------------------------
     if (box[3] - box[1] > 0.f && box[2] - box[0] > 0.f) {
@@ -122,7 +150,7 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
 
     // ---- decoded predictions ---------------------------------------------------------------------------------------------------
     const Dual p_depth = decode_depth(X(c.ch[C_DEPTH]), c);
-    const Dual d_unc = dclamp(X(c.ch[C_DEPTH_UNC]), c.unc_lo, c.unc_hi);
+    const Dual d_unc = has_du ? dclamp(X(c.ch[C_DEPTH_UNC]), c.unc_lo, c.unc_hi) : K(0.f);
     Dual p_dims[3];
     for (int k = 0; k < 3; ++k) {                                   // anno_encoder.py:217-239
         Dual o = X(c.ch[C_DIM] + k);
@@ -130,10 +158,13 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
         p_dims[k] = c.dim_use_std ? o * c.dim_std[cls * 3 + k] + c.dim_mean[cls * 3 + k] : o * c.dim_mean[cls * 3 + k];
     }
     Dual kx[10], ky[10];
-    for (int j = 0; j < 10; ++j) { kx[j] = X(c.ch[C_CORNER] + 2 * j); ky[j] = X(c.ch[C_CORNER] + 2 * j + 1); }
+    for (int j = 0; j < 10; ++j) {
+        kx[j] = has_kp ? X(c.ch[C_CORNER] + 2 * j) : K(0.f);
+        ky[j] = has_kp ? X(c.ch[C_CORNER] + 2 * j + 1) : K(0.f);
+    }
     // depths from the three keypoint groups (anno_encoder.py:185-215); the focal length is the reference's rank-indexed one
-    Dual kd[3];
-    {
+    Dual kd[3] = {K(0.f), K(0.f), K(0.f)};
+    if (has_kp) {
         const Dual fh = p_dims[1] * t[R_FU_RANK];
         auto solve = [&](Dual dh) { return fh / (drelu(dh) * c.down_ratio + c.eps); };
         kd[0] = solve(ky[8] - ky[9]);
@@ -142,15 +173,19 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
         for (int g = 0; g < 3; ++g) kd[g] = dclamp(kd[g], c.depth_range[0], c.depth_range[1]);
     }
     Dual c_unc[3];
-    for (int g = 0; g < 3; ++g) c_unc[g] = dclamp(X(c.ch[C_CORNER_UNC] + g), c.unc_lo, c.unc_hi);
-    // uncertainty-weighted combination of the four depth estimates
+    for (int g = 0; g < 3; ++g) c_unc[g] = has_cu ? dclamp(X(c.ch[C_CORNER_UNC] + g), c.unc_lo, c.unc_hi) : K(0.f);
+    // uncertainty-weighted combination of the depth estimates: all four, or (no depth_uncertainty) the three keypoint depths alone
+    // (detector_loss.py:396-403); without corner_uncertainty there is no combination and `soft` stays 0
     const Dual comb_depth[4] = {p_depth, kd[0], kd[1], kd[2]};
     const Dual comb_unc[4] = {dexp(d_unc), dexp(c_unc[0]), dexp(c_unc[1]), dexp(c_unc[2])};
+    const int c0 = has_du ? 0 : 1;                                   // first column of the combination
     Dual wsum = K(0.f), soft = K(0.f);
-    for (int i = 0; i < 4; ++i) wsum = wsum + K(1.f) / comb_unc[i];
-    for (int i = 0; i < 4; ++i) soft = soft + comb_depth[i] * ((K(1.f) / comb_unc[i]) / wsum);
-    int amin = 0;
-    for (int i = 1; i < 4; ++i) if (comb_unc[i].v < comb_unc[amin].v) amin = i;
+    int amin = c0;
+    if (has_cu) {
+        for (int i = c0; i < 4; ++i) wsum = wsum + K(1.f) / comb_unc[i];
+        for (int i = c0; i < 4; ++i) soft = soft + comb_depth[i] * ((K(1.f) / comb_unc[i]) / wsum);
+        for (int i = c0 + 1; i < 4; ++i) if (comb_unc[i].v < comb_unc[amin].v) amin = i;
+    }
     Dual corner_depth = p_depth;                                     // CORNER_LOSS_DEPTH: direct
     if (c.corner_depth_mode == 1) corner_depth = (kd[0] + kd[1] + kd[2]) / 3.f;
     else if (c.corner_depth_mode == 2) corner_depth = soft;
@@ -176,7 +211,7 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
     // ---- depth with aleatoric uncertainty (detector_loss.py:302-314) -----------------------------------------------------------
     {
         const Dual l1 = dabs(p_depth - t_depth) * c.w[T_DEPTH];
-        out[T_DEPTH] = (l1 * dexp(-d_unc) + d_unc * c.w[T_DEPTH]) * inv_v;
+        out[T_DEPTH] = (has_du ? l1 * dexp(-d_unc) + d_unc * c.w[T_DEPTH] : l1) * inv_v;
         out[V_REAL_DEPTH] = K(l1.v * inv_v);
     }
     // ---- projected-centre offset; truncated objects optionally in their own (log) term -----------------------------------------
@@ -231,41 +266,48 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
         out[V_IOU3D] = K(biou::iou_parts(pl, pd, pc.v, ps.v, tl, t + R_DIMS, tc.v, ts.v) * inv_v);
     }
     // ---- keypoints (visible ones) ----------------------------------------------------------------------------------------------
-    {
+    if (has_kp) {
         Dual l = K(0.f);
         for (int j = 0; j < 10; ++j)
             l = l + (dabs(kx[j] - t[R_KP + 3 * j]) + dabs(ky[j] - t[R_KP + 3 * j + 1])) * t[R_KP + 3 * j + 2];
         out[T_KEYPOINT] = l * (c.w[T_KEYPOINT] / cnt(N_KMASK));
     }
-    // ---- keypoint depths with their uncertainties; invalid groups only train the uncertainty (detector_loss.py:341-371) ---------
-    {
+    // ---- keypoint depths with their uncertainties; invalid groups only train the uncertainty (detector_loss.py:341-371); without
+    // corner_uncertainty the valid ones are plain L1 and the invalid ones a detached constant (value, no gradient) ------------------
+    if (has_kp) {
         Dual l = K(0.f);
         float lg = 0.f;
         for (int g = 0; g < 3; ++g) {
             const float wk = c.w[T_KEYPOINT_DEPTH];
             if (t[R_KDM + g] != 0.f) {
                 const Dual l1 = dabs(kd[g] - t_depth) * wk;
-                l = l + (l1 * dexp(-c_unc[g]) + c_unc[g] * wk) / cnt(N_KD_VALID);
+                l = l + (has_cu ? l1 * dexp(-c_unc[g]) + c_unc[g] * wk : l1) / cnt(N_KD_VALID);
                 lg += l1.v / cnt(N_KD_VALID);
             } else if (c.modify_invalid) {
-                l = l + dabs(detach(kd[g]) - t_depth) * wk * dexp(-c_unc[g]) / cnt(N_KD_INVALID);
+                const Dual l1 = dabs(detach(kd[g]) - t_depth) * wk;
+                l = l + (has_cu ? l1 * dexp(-c_unc[g]) : l1) / cnt(N_KD_INVALID);
             }
         }
         out[T_KEYPOINT_DEPTH] = l;
         out[V_VALID_KD] = K(lg);
     }
     // ---- the combined depth ----------------------------------------------------------------------------------------------------
-    out[T_SOFT_DEPTH] = dabs(soft - t_depth) * (c.w[T_SOFT_DEPTH] * inv_v);
+    if (has_cu) out[T_SOFT_DEPTH] = dabs(soft - t_depth) * (c.w[T_SOFT_DEPTH] * inv_v);
     // ---- logged relative depth errors (detector_loss.py:396-482) ---------------------------------------------------------------
     {
         const float mae[4] = {fabsf(p_depth.v - t_depth) / t_depth, fabsf(kd[0].v - t_depth) / t_depth, fabsf(kd[1].v - t_depth) / t_depth,
                               fabsf(kd[2].v - t_depth) / t_depth};
-        out[V_DEPTH_MAE] = K(mae[0] * inv_v); out[V_CENTER_MAE] = K(mae[1] * inv_v);
-        out[V_02_MAE] = K(mae[2] * inv_v); out[V_13_MAE] = K(mae[3] * inv_v);
-        out[V_LOWER_MAE] = K(fminf(fminf(mae[0], mae[1]), fminf(mae[2], mae[3])) * inv_v);
-        out[V_HARD_MAE] = K(mae[amin] * inv_v);
-        out[V_SOFT_MAE] = K(fabsf(soft.v - t_depth) / t_depth * inv_v);
-        out[V_MEAN_MAE] = K(fabsf(0.25f * (comb_depth[0].v + comb_depth[1].v + comb_depth[2].v + comb_depth[3].v) - t_depth) / t_depth * inv_v);
+        out[V_DEPTH_MAE] = K(mae[0] * inv_v);
+        if (has_kp) { out[V_CENTER_MAE] = K(mae[1] * inv_v); out[V_02_MAE] = K(mae[2] * inv_v); out[V_13_MAE] = K(mae[3] * inv_v); }
+        if (has_cu) {
+            const float lower3 = fminf(mae[1], fminf(mae[2], mae[3]));
+            const float mean = has_du ? 0.25f * (comb_depth[0].v + comb_depth[1].v + comb_depth[2].v + comb_depth[3].v)
+                                      : (comb_depth[1].v + comb_depth[2].v + comb_depth[3].v) / 3.f;
+            out[V_LOWER_MAE] = K((has_du ? fminf(fminf(mae[0], mae[1]), fminf(mae[2], mae[3])) : lower3) * inv_v);
+            out[V_HARD_MAE] = K(mae[amin] * inv_v);
+            out[V_SOFT_MAE] = K(fabsf(soft.v - t_depth) / t_depth * inv_v);
+            out[V_MEAN_MAE] = K(fabsf(mean - t_depth) / t_depth * inv_v);
+        }
     }
 }
 

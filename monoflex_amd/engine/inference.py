@@ -102,7 +102,7 @@ def inference_all_depths(model, data_loader, dataset_name, eval_types=("detectio
     """`--eval_all_depths` (engine/inference.py:131-198): the evaluation once per depth-solving method, each into
     `<output_folder>/eval_all_depths/<method>`, by re-assigning `post_processor.output_depth` between passes (the decode kernel reads the mode
     per launch; 'oracle' needs the ground-truth fields of a validation split).  Logs the Car AP@0.70 bev/3d line per method and the ranking by
-    3D moderate.  -> {method: ret_dict} on rank 0 (the reference returns (None, None, None); the log lines are its product), the attribute restored."""
+    3D moderate.  A reduced head set walks the methods it can serve.  -> {method: ret_dict} on rank 0 (the reference returns (None, None, None); the log lines are its product), the attribute restored."""
     import numpy as np
     import torch.distributed as dist
     logger = logging.getLogger("monoflex.inference")
@@ -113,7 +113,9 @@ def inference_all_depths(model, data_loader, dataset_name, eval_types=("detectio
     rank0 = not (dist.is_available() and dist.is_initialized() and dist.get_rank() != 0)
     ret = {}
     try:
-        for method in EVAL_DEPTH_METHODS:
+        # (a reduced head set serves a subset: lib.HeadSet.output_depths -- the others would raise in the reference, and are refused here)
+        methods = [m for m in EVAL_DEPTH_METHODS if m in post.head_set.output_depths()]
+        for method in methods:
             logger.info("evaluation with depth method: %s", method)
             folder = os.path.join(root, method)
             os.makedirs(folder, exist_ok=True)
@@ -134,11 +136,11 @@ def inference_all_depths(model, data_loader, dataset_name, eval_types=("detectio
     cls, thresh = "Car", 0.7
     logger.info("%s AP@%.2f, %.2f:", cls, thresh, thresh)
     key = lambda kind, level: "%s_%s_%.2f/%s" % (cls, kind, thresh, level)
-    for method in EVAL_DEPTH_METHODS:
+    for method in methods:
         d = ret[method]
         logger.info("bev/3d AP, method %s:", method)
         logger.info("%.4f/%.4f, %.4f/%.4f, %.4f/%.4f", d[key("bev", "easy")], d[key("3d", "easy")], d[key("bev", "moderate")],
                     d[key("3d", "moderate")], d[key("bev", "hard")], d[key("3d", "hard")])
-    order = np.argsort(-np.array([ret[m][key("3d", "moderate")] for m in EVAL_DEPTH_METHODS]))
-    logger.info("Cls %s, Thresh %s, Sort: %s", cls, thresh, " > ".join(EVAL_DEPTH_METHODS[i] for i in order))
+    order = np.argsort(-np.array([ret[m][key("3d", "moderate")] for m in methods]))
+    logger.info("Cls %s, Thresh %s, Sort: %s", cls, thresh, " > ".join(methods[i] for i in order))
     return ret

@@ -119,13 +119,17 @@ class ObjectLossCfg(ctypes.Structure):                          # mfx_object_los
                 ("depth_ref", c_float * 2), ("depth_range", c_float * 2)] + \
         [(n, c_float) for n in ("unc_lo", "unc_hi", "down_ratio", "eps")] + \
         [(n, c_int) for n in ("depth_mode", "has_depth_range", "dim_exp", "dim_use_std", "iou_type", "corner_depth_mode",
-                              "separate_trunc", "trunc_log", "modify_invalid")] + [("ch", c_int * 9)]
+                              "separate_trunc", "trunc_log", "modify_invalid")] + [("ch", c_int * 9), ("reg_width", c_int)]
 
 
 class DecodeCfg(ctypes.Structure):                              # mfx_decode_cfg
     _fields_ = [("dim_mean", c_float * 9), ("dim_std", c_float * 9), ("depth_ref", c_float * 2), ("depth_range", c_float * 2),
                 ("down_ratio", c_float), ("eps", c_float)] + \
         [(n, c_int) for n in ("depth_decode", "dim_exp", "dim_use_std", "uncertainty_as_conf", "output_depth")]
+
+
+class HeadLayout(ctypes.Structure):                             # mfx_head_layout
+    _fields_ = [("ch", c_int * 9), ("reg_width", c_int)]
 
 
 # every symbol include/monoflex_hip.h declares: name -> (restype, argtypes)
@@ -204,6 +208,7 @@ SYMBOLS = {
     "mfx_focal_loss": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
     "mfx_object_loss": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, ctypes.POINTER(ObjectLossCfg), _P, _P, _P]),
     "mfx_object_loss_backward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "mfx_object_loss_backward_width": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "mfx_box3d_iou_pairs": (_I, [_P, _P, _I, _I, _P, _P]),
     "mfx_kitti_encode_targets": (_I, [ctypes.POINTER(KittiDesc), _P]),
     "mfx_kitti_encode_targets_views": (_I, [ctypes.POINTER(KittiDesc), _P, _P]),
@@ -215,6 +220,8 @@ SYMBOLS = {
     "mfx_decode_boxes": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P]),
     "mfx_decode_boxes_mode": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _P, _P, _P]),
     "mfx_decode_boxes_cfg": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.POINTER(DecodeCfg), _P, _P, _P, _P, _P]),
+    "mfx_decode_boxes_heads": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.POINTER(DecodeCfg), ctypes.POINTER(HeadLayout),
+                                    _P, _P, _P, _P, _P]),
 }
 
 # mfx_decode_boxes_mode's depth_mode (include/monoflex_hip.h MFX_DEPTH_*), by the reference's `output_depth` names (detector_infer.py:149-198)
@@ -233,6 +240,115 @@ def head_decode_settings(cfg):
                 dim_mean=tuple(tuple(float(v) for v in row) for row in H.DIMENSION_MEAN),
                 dim_std=tuple(tuple(float(v) for v in row) for row in H.DIMENSION_STD),
                 dim_modes=list(H.DIMENSION_REG), down_ratio=cfg.MODEL.BACKBONE.DOWN_RATIO, eps=1e-3)
+
+
+# The nine regression keys in the order of mfx_object_loss_cfg.ch[] / mfx_head_layout.ch[], with their widths
+HEAD_KEYS = ('2d_dim', '3d_offset', 'corner_offset', 'corner_uncertainty', '3d_dim', 'ori_cls', 'ori_offset', 'depth', 'depth_uncertainty')
+HEAD_WIDTHS = dict(zip(HEAD_KEYS, (4, 2, 20, 3, 3, 8, 8, 1, 1)))
+HEAD_OPTIONAL = ('depth_uncertainty', 'corner_offset', 'corner_uncertainty')
+CORNER_DEPTHS = ('direct', 'keypoint_mean', 'soft_combine', 'hard_combine')        # mfx_object_loss_cfg.corner_depth_mode
+LOSS_REQUIRED = ('hm_loss', 'bbox_loss', 'depth_loss', 'offset_loss', 'orien_loss', 'dims_loss')
+LOSS_OPTIONAL = ('corner_loss', 'trunc_offset_loss', 'keypoint_loss', 'keypoint_depth_loss', 'weighted_avg_depth_loss')
+
+
+class HeadSet:
+    """The head set of a config: which of the reference's regression keys the model predicts and where each starts in the R-wide
+    regression row (MODEL.HEAD.REGRESSION_HEADS / REGRESSION_CHANNELS flattened, as Converter_key2channel).  Read ONCE for every user --
+    the loss evaluator, the post-processor and the predictor take starts, R and what the set can serve from here, in the spirit of
+    head_decode_settings().  `du`, `kp`, `cu`: depth_uncertainty / corner_offset / corner_uncertainty present."""
+
+    def __init__(self, regression_heads, regression_channels):
+        names = [n for group in regression_heads for n in group]
+        widths = [int(w) for group in regression_channels for w in group]
+        if len(names) != len(widths) or [len(g) for g in regression_heads] != [len(g) for g in regression_channels]:
+            raise NotImplementedError("head set: REGRESSION_HEADS and REGRESSION_CHANNELS do not pair up: %r / %r" % (regression_heads, regression_channels))
+        bad = [n for n in names if n not in HEAD_KEYS] + [n for n in set(names) if names.count(n) > 1]
+        if bad:
+            raise NotImplementedError("head set: unknown or repeated regression keys %s (known: %s)" % (sorted(set(bad)), ", ".join(HEAD_KEYS)))
+        missing = [k for k in HEAD_KEYS if k not in names and k not in HEAD_OPTIONAL]
+        if missing:
+            raise NotImplementedError("head set %s: the required keys %s are missing" % (names, missing))
+        wrong = ["%s(%d)" % (n, w) for n, w in zip(names, widths) if HEAD_WIDTHS[n] != w]
+        if wrong:
+            raise NotImplementedError("head set: channel counts %s differ from the reference's %s" % (wrong, [HEAD_WIDTHS[n] for n in names]))
+        self.names, self.widths = names, widths
+        self.starts, start = {}, 0
+        for n, w in zip(names, widths):
+            self.starts[n] = start
+            start += w
+        self.R = start
+        self.du, self.kp, self.cu = ('depth_uncertainty' in names), ('corner_offset' in names), ('corner_uncertainty' in names)
+        if self.cu and not self.kp:
+            raise NotImplementedError("head set %s: corner_uncertainty without corner_offset" % (names,))
+        self.full = self.du and self.kp and self.cu
+
+    def describe(self):
+        return "head set (depth_uncertainty %d, corner_offset %d, corner_uncertainty %d; %d channels)" % (self.du, self.kp, self.cu, self.R)
+
+    def ch(self, key):
+        """First channel of `key` in the regression row, -1 when the set does not have it."""
+        return self.starts.get(key, -1)
+
+    def corner_depths(self):
+        """The CORNER_LOSS_DEPTH values this set can serve (the reference raises on the others)."""
+        return CORNER_DEPTHS[:1] + (CORNER_DEPTHS[1:2] if self.kp else ()) + (CORNER_DEPTHS[2:] if self.full else ())
+
+    def output_depths(self):
+        """The OUTPUT_DEPTH values this set can serve (detector_infer.py:148-204)."""
+        out = ('direct',)
+        if self.kp:
+            out += ('keypoints_avg', 'keypoints_center', 'keypoints_02', 'keypoints_13')
+        if self.cu:
+            out += ('soft', 'hard', 'mean', 'oracle')
+        return out
+
+    def oracle_columns(self):
+        """The single-estimate decodes 'oracle' chooses among: the reference's pred_combined_depths columns (detector_infer.py:177-182)."""
+        return (('direct',) if self.du else ()) + ('keypoints_center', 'keypoints_02', 'keypoints_13')
+
+    def has_depth_error(self, output_depth):
+        """Whether the reference has an estimated_depth_error under `output_depth` (None otherwise: raw score, eval_utils entries None)."""
+        if output_depth == 'direct':
+            return self.du
+        return self.cu
+
+    def check_corner_depth(self, corner_loss_depth):
+        if corner_loss_depth not in self.corner_depths():
+            raise NotImplementedError("CORNER_LOSS_DEPTH %r with the %s: this set serves %s"
+                                      % (corner_loss_depth, self.describe(), ", ".join(self.corner_depths())))
+
+    def check_output_depth(self, output_depth):
+        if output_depth not in self.output_depths():
+            raise NotImplementedError("OUTPUT_DEPTH %r with the %s: this set serves %s"
+                                      % (output_depth, self.describe(), ", ".join(self.output_depths())))
+
+    def check_loss_names(self, loss_names):
+        """LOSS_NAMES the set can serve: the six basic terms always, keypoint_loss iff corner_offset (the reference indexes its weight
+        unconditionally), keypoint_depth_loss only with corner_offset, weighted_avg_depth_loss only with corner_uncertainty."""
+        names = list(loss_names)
+        problems = ["%s is required" % n for n in LOSS_REQUIRED if n not in names]
+        problems += ["%s is not a loss of the reference" % n for n in names if n not in LOSS_REQUIRED + LOSS_OPTIONAL]
+        if self.kp and 'keypoint_loss' not in names:
+            problems.append("keypoint_loss is required with corner_offset")
+        if not self.kp:
+            problems += ["%s needs corner_offset" % n for n in ('keypoint_loss', 'keypoint_depth_loss') if n in names]
+        if not self.cu and 'weighted_avg_depth_loss' in names:
+            problems.append("weighted_avg_depth_loss needs corner_offset and corner_uncertainty")
+        if problems:
+            raise NotImplementedError("LOSS_NAMES %s with the %s: %s" % (names, self.describe(), "; ".join(problems)))
+
+    def layout(self):
+        """mfx_head_layout of this set."""
+        h = HeadLayout()
+        for i, key in enumerate(HEAD_KEYS):
+            h.ch[i] = self.ch(key)
+        h.reg_width = self.R
+        return h
+
+
+def head_set(cfg):
+    """HeadSet of a config's MODEL.HEAD.REGRESSION_HEADS / REGRESSION_CHANNELS."""
+    return HeadSet(cfg.MODEL.HEAD.REGRESSION_HEADS, cfg.MODEL.HEAD.REGRESSION_CHANNELS)
 
 
 def fill_decode_settings(c, s):

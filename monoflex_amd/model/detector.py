@@ -56,7 +56,7 @@ class KeypointDetector(nn.Module):
         return det, topk, valid, hm
 
     def forward_train_maps(self, images, edge_indices, edge_lens):
-        """Training-mode network: (B,3,H,W) images -> (class logits (B,h,w,ncls), regression (B,h,w,50)), NHWC,
+        """Training-mode network: (B,3,H,W) images -> (class logits (B,h,w,ncls), regression (B,h,w,R)), NHWC,
         differentiable (HIP forward + backward kernels; BN on batch statistics)."""
         feat = self.backbone.forward_nhwc(images)
         return self.heads.predictor.forward_train(feat, edge_indices, edge_lens)

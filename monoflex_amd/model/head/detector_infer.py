@@ -34,14 +34,15 @@ class PostProcessor(nn.Module):
         self.num_classes = len(cfg.DATASETS.DETECT_CLASSES)
         # What the decode kernel cannot do is refused; every head setting the loss evaluator accepts (DEPTH_MODE, DEPTH_REFERENCE,
         # DEPTH_RANGE, DIMENSION_REG, DIMENSION_MEAN / _STD) and TEST.UNCERTAINTY_AS_CONFIDENCE reach it through mfx_decode_cfg.
-        want = ['2d_dim', '3d_offset', 'corner_offset', 'corner_uncertainty', '3d_dim', 'ori_cls', 'ori_offset',
-                'depth', 'depth_uncertainty']
+        # The head set (lib.HeadSet, the loss evaluator's reading too) decides which OUTPUT_DEPTH can be served: what the reference raises on
+        # is refused here.
+        hs = self.head_set = L.HeadSet([key2channel.keys], [key2channel.channels])
         s = self.decode_settings = L.head_decode_settings(cfg)      # the same reading of the config as Loss_Computation's
         refused = []
-        if key2channel.keys != want or key2channel.channels != [4, 2, 20, 3, 3, 8, 8, 1, 1]:
-            refused.append("regression heads other than the nine-key 50-channel layout of runs/monoflex.yaml")
         if self.output_depth not in L.DEPTH_MODES and self.output_depth != 'oracle':
             refused.append("OUTPUT_DEPTH %r" % (self.output_depth,))
+        else:
+            hs.check_output_depth(self.output_depth)
         if cfg.INPUT.ORIENTATION != 'multi-bin' or cfg.INPUT.ORIENTATION_BIN_SIZE != 4:
             refused.append("an orientation other than multi-bin with 4 bins")
         if s["down_ratio"] != 4:
@@ -57,6 +58,8 @@ class PostProcessor(nn.Module):
         if refused:
             raise NotImplementedError("the HIP decode kernel does not implement: " + "; ".join(refused))
         self.decode_cfg = L.decode_cfg(s, self.uncertainty_as_conf)
+        self.head_layout = hs.layout()
+        self.reg_width = hs.R
 
     @staticmethod
     def prepare_targets(targets, device):
@@ -74,8 +77,9 @@ class PostProcessor(nn.Module):
             raise ValueError("output_depth = 'oracle' reads the ground truth of each image: call the module (forward) with the dataset's targets")
         scores, index = ops.decode_topk(hm, 0, self.num_classes, self.max_detection, planar=cls_planar)
         # (`output_depth` is read at every call: engine/inference.py:166 re-assigns it between the passes of `eval_all_depths`)
+        self.head_set.check_output_depth(self.output_depth)
         return ops.decode_boxes(hm, REG_OFF, scores, index, calib, pad, size, float(self.det_threshold), depth_mode=self.output_depth,
-                                cfg=self.decode_cfg, return_unc=return_unc)
+                                cfg=self.decode_cfg, return_unc=return_unc, heads=self.head_layout)
 
     def forward(self, predictions, targets, features=None, test=False, refine_module=None):
         hm = predictions['hm_nhwc']
@@ -88,30 +92,32 @@ class PostProcessor(nn.Module):
         results = [det[b][keep[b]] for b in range(det.shape[0])]          # host sync, as detector_infer.py:106
         vis_scores = [topk[b][keep[b], 0] for b in range(det.shape[0])]
         one = lambda rows: rows[0] if len(results) == 1 else rows
-        # detector_infer.py:223-229,234-235: the valid rows' values under UNCERTAINTY_AS_CONFIDENCE, None without it
-        depth_error = one([unc[b][keep[b], 0] for b in range(det.shape[0])]) if self.uncertainty_as_conf else None
-        unc_conf = one([unc[b][keep[b], 1] for b in range(det.shape[0])]) if self.uncertainty_as_conf else None
+        # detector_infer.py:223-229,234-235: the valid rows' values under UNCERTAINTY_AS_CONFIDENCE, None without it -- and None where the head
+        # set has no uncertainty head for the chosen depth (estimated_depth_error is None there: the score stays raw)
+        report = self.uncertainty_as_conf and self.head_set.has_depth_error(self.output_depth)
+        depth_error = one([unc[b][keep[b], 0] for b in range(det.shape[0])]) if report else None
+        unc_conf = one([unc[b][keep[b], 1] for b in range(det.shape[0])]) if report else None
         eval_utils = {'dis_ious': None, 'depth_errors': None, 'vis_scores': one(vis_scores), 'uncertainty_conf': unc_conf,
                       'estimated_depth_error': depth_error, 'topk': topk, 'valid': valid, 'det_all': det}
         visualize_preds = {'heat_map': predictions['cls']}
         result = results[0] if len(results) == 1 else results
         return result, eval_utils, visualize_preds
 
-    # the single-estimate decodes whose rows `decode_oracle` chooses among, in the column order of the reference's
-    # pred_combined_depths (detector_infer.py:173: direct, then the three keypoint groups)
-    ORACLE_COLUMNS = ('direct', 'keypoints_center', 'keypoints_02', 'keypoints_13')
-
     def decode_oracle(self, hm, pad, calib, size, cls_planar, targets):
         """`output_depth = 'oracle'` (detector_infer.py:199-202, get_oracle_depths :238-277; the first method engine/inference.py:154 evaluates):
-        every detection takes, of its four depth estimates, the one closest to the depth of the ground-truth object it overlaps (nearest box centre
+        every detection takes, of its four (three without depth_uncertainty) depth estimates, the one closest to the depth of the ground-truth object it overlaps (nearest box centre
         of its class, 2D IoU >= 0.5), and the mean of the four when it overlaps none.  The depth only enters a row through location, rotation and
         the uncertainty-scaled score, so the row of a detection under 'oracle' IS its row from the decode of the chosen single estimate (or of
         'mean'): five launches of the box kernel on one top-K, and a per-detection choice of row on the host, where the ground truth is.
         (The reference reads targets[0] only -- it evaluates at batch 1; here image b reads targets[b].)"""
         scores, index = ops.decode_topk(hm, 0, self.num_classes, self.max_detection, planar=cls_planar)
+        # the single-estimate decodes whose rows are chosen among, in the column order of the reference's pred_combined_depths
+        # (detector_infer.py:173-182): direct, then the three keypoint groups -- the three alone for a head set without depth_uncertainty
+        self.head_set.check_output_depth('oracle')
+        columns = self.head_set.oracle_columns()
         dec = {m: ops.decode_boxes(hm, REG_OFF, scores, index, calib, pad, size, float(self.det_threshold), depth_mode=m, cfg=self.decode_cfg,
-                                   return_unc=True)
-               for m in ('mean',) + self.ORACLE_COLUMNS}
+                                   return_unc=True, heads=self.head_layout)
+               for m in ('mean',) + columns}
         det, topk, valid, _ = dec['mean']
         rows = {m: d[0].cpu() for m, d in dec.items()}
         uncs = {m: d[3].cpu() for m, d in dec.items()}
@@ -132,8 +138,8 @@ class PostProcessor(nn.Module):
                 near = int(torch.argmin(dis))
                 if _box_iou(box.numpy(), gt_box[near].numpy()) < 0.5:            # (a 0 / 0 overlap is not "< 0.5": such a pair counts as met, :268-270)
                     continue
-                est = torch.stack([rows[m][b, i, 11] for m in self.ORACLE_COLUMNS])     # row[11] = location z = the depth that decode used
-                chosen = self.ORACLE_COLUMNS[int(torch.argmin(torch.abs(est - gt_depth[near])))]
+                est = torch.stack([rows[m][b, i, 11] for m in columns])     # row[11] = location z = the depth that decode used
+                chosen = columns[int(torch.argmin(torch.abs(est - gt_depth[near])))]
                 out[b, i], out_unc[b, i] = rows[chosen][b, i], uncs[chosen][b, i]
         return out.to(det.device), topk, valid, out_unc.to(det.device)
 

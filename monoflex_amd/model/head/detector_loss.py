@@ -3,8 +3,9 @@ model/anno_encoder.py:88-295, model/layers/focal_loss.py:29-55, model/layers/iou
 model/layers/utils.py:120-145, data/datasets/kitti_utils.py:350-369).
 
 Same constructor, `prepare_targets`, `__call__(predictions, targets) -> (loss_dict, log_loss_dict)`, the same 11
-loss names, weights and values.  The formulation differs: the reference compacts the valid objects with boolean
-indexing (dynamic shapes, one host sync per index, ~30 `.item()` calls); here every per-object quantity keeps its
+loss names, weights and values, for every head set the reference itself can train (lib.HeadSet: depth_uncertainty,
+corner_offset and corner_uncertainty are optional heads; a loss name or logged key the reference leaves out is left out).
+The formulation differs: the reference compacts the valid objects with boolean indexing (dynamic shapes, one host sync per index, ~30 `.item()` calls); here every per-object quantity keeps its
 static (B*MAX_OBJECTS) shape and selections are 0/1 weights, so
 
     mean over selected rows  ==  sum(w * v) / sum(w)
@@ -62,16 +63,13 @@ class Loss_Computation:
         self.separate_trunc_offset = 'trunc_offset_loss' in self.loss_keys
         self.modify_invalid_keypoint_depths = H.MODIFY_INVALID_KEYPOINT_DEPTH
         self.corner_loss_depth = H.CORNER_LOSS_DEPTH
-        keys = self.key2channel.keys
-        need = ('2d_dim', '3d_offset', 'corner_offset', 'corner_uncertainty', '3d_dim', 'ori_cls', 'ori_offset', 'depth',
-                'depth_uncertainty')
-        names = ('hm_loss', 'bbox_loss', 'depth_loss', 'offset_loss', 'orien_loss', 'dims_loss', 'corner_loss', 'keypoint_loss',
-                 'keypoint_depth_loss', 'weighted_avg_depth_loss')
-        if any(k not in keys for k in need) or any(n not in self.loss_keys for n in names) \
-                or self.corner_loss_depth not in ('soft_combine', 'hard_combine', 'direct', 'keypoint_mean'):
-            raise NotImplementedError("Loss_Computation is built for the head/loss set of runs/monoflex.yaml")
-        # Anno_Encoder constants (anno_encoder.py:11-48)
+        # the head set (which optional heads the model predicts) decides what can be asked of this evaluator: everything the reference
+        # itself raises on is refused here, at construction
         from ... import lib as L
+        hs = self.head_set = L.head_set(cfg)
+        hs.check_corner_depth(self.corner_loss_depth)
+        hs.check_loss_names(self.loss_keys)
+        # Anno_Encoder constants (anno_encoder.py:11-48)
         s = self.decode_settings = L.head_decode_settings(cfg)      # one reading of the config for this evaluator and the post-processor's decode
         self.depth_mode, self.depth_range = s["depth_mode"], s["depth_range"]
         self.depth_ref = s["depth_ref"]
@@ -138,7 +136,7 @@ class Loss_Computation:
         from ... import lib as L
         if getattr(self, "_obj_cfg", None) is not None:
             return self._obj_cfg
-        W, k = self.loss_weights, self.key2channel
+        W = self.loss_weights
         if self.orien_bin_size != 4 or self.depth_mode not in ('exp', 'linear', 'inv_sigmoid') or self.depth_range is None \
                 or len(self.dim_mean) != 3:
             return None
@@ -154,12 +152,12 @@ class Loss_Computation:
         c.unc_lo, c.unc_hi = float(lo), float(hi)
         c.has_depth_range = 1
         c.iou_type = ('giou', 'iou', 'linear_iou').index(self.iou_type)
-        c.corner_depth_mode = ('direct', 'keypoint_mean', 'soft_combine', 'hard_combine').index(self.corner_loss_depth)
+        c.corner_depth_mode = L.CORNER_DEPTHS.index(self.corner_loss_depth)
         c.separate_trunc, c.trunc_log = int(self.separate_trunc_offset), int(self.trunc_offset_loss_type != 'L1')
         c.modify_invalid = int(bool(self.modify_invalid_keypoint_depths))
-        for i, key in enumerate(('2d_dim', '3d_offset', 'corner_offset', 'corner_uncertainty', '3d_dim', 'ori_cls', 'ori_offset', 'depth',
-                                 'depth_uncertainty')):
-            c.ch[i] = k(key).start
+        for i, key in enumerate(L.HEAD_KEYS):
+            c.ch[i] = self.head_set.ch(key)                   # -1: the set does not have this (optional) head
+        c.reg_width = self.head_set.R
         self._obj_cfg = c
         return c
 
@@ -265,20 +263,25 @@ class Loss_Computation:
         p_depth = self._decode_depth(poi[:, k('depth')].squeeze(-1))
         preds['depth_3D'] = p_depth
         lo, hi = (self.uncertainty_range if self.uncertainty_range is not None else (-float('inf'), float('inf')))
-        preds['depth_uncertainty'] = torch.clamp(poi[:, k('depth_uncertainty')].squeeze(-1), min=lo, max=hi)
+        hs = self.head_set
+        if hs.du:
+            preds['depth_uncertainty'] = torch.clamp(poi[:, k('depth_uncertainty')].squeeze(-1), min=lo, max=hi)
         kp = tv["keypoints"].reshape(N, -1, 3).to(reg.dtype)
         targets['keypoints'], targets['keypoints_mask'] = kp[..., :2], kp[..., 2] * v[:, None]
         kdm = tv["keypoints_depth_mask"].reshape(N, 3).bool()
         targets['keypoints_depth_mask'] = kdm
-        p_kp = poi[:, k('corner_offset')].reshape(N, -1, 2)
+        if hs.kp:
+            p_kp = poi[:, k('corner_offset')].reshape(N, -1, 2)
         # the reference indexes the calibration list by the RANK of the image among those that own an object
         # (anno_encoder.py:198-199, `calibs[idx]` not `calibs[gt_idx]`) -- kept
         present = tv["reg_mask"].reshape(B, -1).bool().any(dim=1)
         rank = (torch.cumsum(present.long(), 0) - 1).clamp(min=0)
         f_u = tv["calib_f32"][:, 0][rank][bidx]
-        preds['keypoints'] = p_kp
-        preds['keypoints_depths'] = self._keypoint_depths(p_kp, p_dims, f_u)
-        preds['corner_offset_uncertainty'] = torch.clamp(poi[:, k('corner_uncertainty')], min=lo, max=hi)
+        if hs.kp:
+            preds['keypoints'] = p_kp
+            preds['keypoints_depths'] = self._keypoint_depths(p_kp, p_dims, f_u)
+        if hs.cu:
+            preds['corner_offset_uncertainty'] = torch.clamp(poi[:, k('corner_uncertainty')], min=lo, max=hi)
         if self.corner_loss_depth == 'direct':
             corner_depth = p_depth
         elif self.corner_loss_depth == 'keypoint_mean':
@@ -360,30 +363,50 @@ class Loss_Computation:
         if cfg is None or rows is None:
             raise NotImplementedError("fused object loss: 4 orientation bins, 10 keypoints, a depth range")
         if predictions.get('reg') is None:
-            terms, logged = AG.ObjectLossFn.apply(predictions['reg_rows'].float(), rows.to(dev), cfg, 0)      # (N,50): row n = object row n
+            terms, logged = AG.ObjectLossFn.apply(predictions['reg_rows'].float(), rows.to(dev), cfg, 0)      # (N,R): row n = object row n
         else:
             reg = predictions['reg'].permute(0, 2, 3, 1)                          # the predictor's NHWC map: a view
             terms, logged = AG.ObjectLossFn.apply(reg.float(), rows.to(dev), cfg, 0)
         t = terms.unbind(0)
         loss_dict = _LossDict({'hm_loss': self._heat_term(predictions, heat, dev), 'bbox_loss': t[0], 'dims_loss': t[5], 'orien_loss': t[4],
                                'offset_loss': t[2]})
-        if self.separate_trunc_offset and terms.shape[0] == 10:
-            loss_dict.total = terms.sum() + loss_dict['hm_loss']           # every entry of `terms` is one of the dict's terms
+        has = lambda name: name in self.loss_keys                                  # noqa: E731
+        # `total`: every entry of `terms` is one of the dict's terms -- or exactly 0: an absent head's terms and an unused trunc_offset term are
+        # never written, and a name that is left out has weight 0, which gives 0 as long as its other factors are finite (exp(-u) under a finite
+        # UNCERTAINTY_RANGE).  Without `total` the trainer adds the dict's entries one by one, and the backward of `terms.unbind()` then fills
+        # the unused entries' gradients with zero-fill nodes of its own: a captured step should not contain those (csrc/fill.h).
+        if terms.shape[0] == 10 and (all(n in self.loss_keys for n in L.LOSS_OPTIONAL) or self.uncertainty_range is not None):
+            loss_dict.total = terms.sum() + loss_dict['hm_loss']
         if self.separate_trunc_offset:
             loss_dict['trunc_offset_loss'] = t[3]
-        loss_dict.update({'corner_loss': t[6], 'depth_loss': t[1], 'keypoint_loss': t[7], 'keypoint_depth_loss': t[8],
-                          'weighted_avg_depth_loss': t[9]})
+        # a loss name the config leaves out is left out of the dict (its kernel term is 0: zero weight or an absent head), as in the reference
+        for name, i in (('corner_loss', 6), ('depth_loss', 1), ('keypoint_loss', 7), ('keypoint_depth_loss', 8), ('weighted_avg_depth_loss', 9)):
+            if has(name):
+                loss_dict[name] = t[i]
         with torch.no_grad():
             lg = logged.unbind(0)
-            logs = {'2D_IoU': lg[0], '3D_IoU': lg[11], 'depth_loss': lg[1], 'keypoint_depth_loss': lg[2]}
+            logs = {'2D_IoU': lg[0], '3D_IoU': lg[11], 'depth_loss': lg[1]}
+            if has('keypoint_depth_loss'):
+                logs['keypoint_depth_loss'] = lg[2]
             for key, val in loss_dict.items():
                 if key not in logs:
                     logs[key] = val.detach()
-            logs.update(dict(zip(('depth_MAE', 'center_MAE', '02_MAE', '13_MAE', 'lower_MAE', 'hard_MAE', 'soft_MAE', 'mean_MAE'), lg[3:11])))
+            logs.update(dict(zip(self._mae_names(), [lg[3 + i] for i in self._mae_slots()])))
             if self.log_as_float:
                 vals = torch.stack([x.float() for x in logs.values()]).tolist()     # the step's single host sync
                 logs = dict(zip(logs.keys(), vals))
         return loss_dict, logs
+
+    _MAE_NAMES = ('depth_MAE', 'center_MAE', '02_MAE', '13_MAE', 'lower_MAE', 'hard_MAE', 'soft_MAE', 'mean_MAE')
+
+    def _mae_slots(self):
+        """Which of the eight logged depth errors the reference reports for this head set (detector_loss.py:450-470): depth_MAE always, the
+        three keypoint ones with corner_offset, the four of the combination with corner_uncertainty."""
+        hs = self.head_set
+        return [0] + ([1, 2, 3] if hs.kp else []) + ([4, 5, 6, 7] if hs.cu else [])
+
+    def _mae_names(self):
+        return [self._MAE_NAMES[i] for i in self._mae_slots()]
 
     def __call__(self, predictions, targets):
         dev = (predictions['reg'] if predictions.get('reg') is not None else predictions['reg_rows']).device
@@ -412,7 +435,12 @@ class Loss_Computation:
         # direct depth with aleatoric uncertainty
         d_l1 = W['depth_loss'] * (P['depth_3D'] - T['depth_3D']).abs()
         real_depth_loss = _wmean(d_l1.detach(), v)
-        depth_loss = _wmean(d_l1 * torch.exp(-P['depth_uncertainty']) + P['depth_uncertainty'] * W['depth_loss'], v)
+        hs = self.head_set
+        has = lambda name: name in self.loss_keys                                  # noqa: E731
+        if hs.du:
+            depth_loss = _wmean(d_l1 * torch.exp(-P['depth_uncertainty']) + P['depth_uncertainty'] * W['depth_loss'], v)
+        else:
+            depth_loss = _wmean(d_l1, v)
 
         # projected-centre offset: L1 inside, log(1+L1) for truncated objects
         off_l1 = (P['offset_3D'] - T['offset_3D']).abs().sum(dim=1)
@@ -427,55 +455,70 @@ class Loss_Computation:
         orien_loss = W['orien_loss'] * self._multibin(P['orien_3D'], T['orien_3D'], v)
         dims_l1 = (P['dims_3D'] - T['dims_3D']).abs() * self._const('dim_weight', self.dim_weight, dev)
         dims_loss = W['dims_loss'] * _wmean(dims_l1.sum(dim=1), v)
-        # (N,8) per-corner L1 sums averaged over all N*8 entries (detector_loss.py:338-339: `.sum(dim=2).mean()`)
-        corner_loss = W['corner_loss'] * _wmean((P['corners_3D'] - T['corners_3D']).abs().sum(dim=2).mean(dim=1), v)
-        kmask = T['keypoints_mask']
-        kp_l1 = (P['keypoints'] - T['keypoints']).abs().sum(dim=2)
-        keypoint_loss = (W['keypoint_loss'] * kp_l1 * kmask).sum() / torch.clamp(kmask.sum(), min=1)
-
-        # depths solved from the three keypoint groups
-        kd = P['keypoints_depths']
-        km = (T['keypoints_depth_mask'] & valid[:, None]).float()
-        kinv = ((~T['keypoints_depth_mask']) & valid[:, None]).float()
-        t_kd = T['depth_3D'].unsqueeze(-1)
-        unc = P['corner_offset_uncertainty']
-        kd_valid = W['keypoint_depth_loss'] * (kd - t_kd).abs()
-        kd_invalid = W['keypoint_depth_loss'] * (kd.detach() - t_kd).abs()
-        log_valid_kd = _wmean(kd_valid.detach(), km)
-        kd_valid = kd_valid * torch.exp(-unc) + W['keypoint_depth_loss'] * unc
-        kd_invalid = kd_invalid * torch.exp(-unc)
-        keypoint_depth_loss = _wmean(kd_valid, km)
-        if self.modify_invalid_keypoint_depths:
-            keypoint_depth_loss = keypoint_depth_loss + _wmean(kd_invalid, kinv)
-
-        comb_depth = torch.cat((P['depth_3D'].unsqueeze(1), kd), dim=1)
-        comb_unc = torch.cat((P['depth_uncertainty'].unsqueeze(1), unc), dim=1).exp()
-        cw = 1 / comb_unc
-        cw = cw / cw.sum(dim=1, keepdim=True)
-        soft_depths = torch.sum(comb_depth * cw, dim=1)
-        soft_depth_loss = W['weighted_avg_depth_loss'] * _wmean((soft_depths - T['depth_3D']).abs(), v)
-
         loss_dict = {'hm_loss': hm_loss, 'bbox_loss': reg_2D_loss, 'dims_loss': dims_loss, 'orien_loss': orien_loss,
                      'offset_loss': offset_loss}
         if self.separate_trunc_offset:
             loss_dict['trunc_offset_loss'] = trunc_offset_loss
-        loss_dict.update({'corner_loss': corner_loss, 'depth_loss': depth_loss, 'keypoint_loss': keypoint_loss,
-                          'keypoint_depth_loss': keypoint_depth_loss, 'weighted_avg_depth_loss': soft_depth_loss})
+        if has('corner_loss'):
+            # (N,8) per-corner L1 sums averaged over all N*8 entries (detector_loss.py:338-339: `.sum(dim=2).mean()`)
+            loss_dict['corner_loss'] = W['corner_loss'] * _wmean((P['corners_3D'] - T['corners_3D']).abs().sum(dim=2).mean(dim=1), v)
+        loss_dict['depth_loss'] = depth_loss
+        mae = {'depth_MAE': _wmean(depth_MAE.detach(), v)}
+        log_valid_kd = None
+        if hs.kp:
+            kmask = T['keypoints_mask']
+            kp_l1 = (P['keypoints'] - T['keypoints']).abs().sum(dim=2)
+            loss_dict['keypoint_loss'] = (W['keypoint_loss'] * kp_l1 * kmask).sum() / torch.clamp(kmask.sum(), min=1)
+
+            # depths solved from the three keypoint groups
+            kd = P['keypoints_depths']
+            t_kd = T['depth_3D'].unsqueeze(-1)
+            if has('keypoint_depth_loss'):
+                km = (T['keypoints_depth_mask'] & valid[:, None]).float()
+                kinv = ((~T['keypoints_depth_mask']) & valid[:, None]).float()
+                kd_valid = W['keypoint_depth_loss'] * (kd - t_kd).abs()
+                kd_invalid = W['keypoint_depth_loss'] * (kd.detach() - t_kd).abs()
+                log_valid_kd = _wmean(kd_valid.detach(), km)
+                if hs.cu:
+                    unc = P['corner_offset_uncertainty']
+                    kd_valid = kd_valid * torch.exp(-unc) + W['keypoint_depth_loss'] * unc
+                    kd_invalid = kd_invalid * torch.exp(-unc)
+                keypoint_depth_loss = _wmean(kd_valid, km)
+                if self.modify_invalid_keypoint_depths:
+                    keypoint_depth_loss = keypoint_depth_loss + _wmean(kd_invalid, kinv)
+                loss_dict['keypoint_depth_loss'] = keypoint_depth_loss
+            with torch.no_grad():
+                kMAE = (kd - t_kd).abs() / t_depth_safe.unsqueeze(-1)
+                mae.update({'center_MAE': _wmean(kMAE[:, 0], v), '02_MAE': _wmean(kMAE[:, 1], v), '13_MAE': _wmean(kMAE[:, 2], v)})
+        if hs.cu:
+            # the combination: all four estimates, or (no depth_uncertainty) the three keypoint depths alone (detector_loss.py:396-403)
+            unc = P['corner_offset_uncertainty']
+            if hs.du:
+                comb_depth = torch.cat((P['depth_3D'].unsqueeze(1), kd), dim=1)
+                comb_unc = torch.cat((P['depth_uncertainty'].unsqueeze(1), unc), dim=1).exp()
+                cMAE = torch.cat((depth_MAE.detach().unsqueeze(1), kMAE), dim=1)
+            else:
+                comb_depth, comb_unc, cMAE = kd, unc.exp(), kMAE
+            cw = 1 / comb_unc
+            cw = cw / cw.sum(dim=1, keepdim=True)
+            soft_depths = torch.sum(comb_depth * cw, dim=1)
+            if has('weighted_avg_depth_loss'):
+                loss_dict['weighted_avg_depth_loss'] = W['weighted_avg_depth_loss'] * _wmean((soft_depths - T['depth_3D']).abs(), v)
+            with torch.no_grad():
+                hard = cMAE.gather(1, comb_unc.argmin(dim=1, keepdim=True)).squeeze(1)
+                mae.update({'lower_MAE': _wmean(cMAE.min(dim=1)[0], v), 'hard_MAE': _wmean(hard, v),
+                            'soft_MAE': _wmean((soft_depths - T['depth_3D']).abs() / t_depth_safe, v),
+                            'mean_MAE': _wmean((comb_depth.mean(dim=1) - T['depth_3D']).abs() / t_depth_safe, v)})
 
         with torch.no_grad():                                                      # log-only quantities (detector_loss.py:396-482)
-            kMAE = (kd - t_kd).abs() / t_depth_safe.unsqueeze(-1)
-            cMAE = torch.cat((depth_MAE.unsqueeze(1), kMAE), dim=1)
-            hard = cMAE.gather(1, comb_unc.argmin(dim=1, keepdim=True)).squeeze(1)
             logs = {'2D_IoU': _wmean(iou2d, v2), '3D_IoU': _wmean(get_iou_3d(P['corners_3D'], T['corners_3D']), v),
-                    'depth_loss': real_depth_loss, 'keypoint_depth_loss': log_valid_kd}
+                    'depth_loss': real_depth_loss}
+            if log_valid_kd is not None:
+                logs['keypoint_depth_loss'] = log_valid_kd
             for key, val in loss_dict.items():
                 if key not in logs:
                     logs[key] = val.detach()
-            logs.update({'depth_MAE': _wmean(depth_MAE, v), 'center_MAE': _wmean(kMAE[:, 0], v),
-                         '02_MAE': _wmean(kMAE[:, 1], v), '13_MAE': _wmean(kMAE[:, 2], v),
-                         'lower_MAE': _wmean(cMAE.min(dim=1)[0], v), 'hard_MAE': _wmean(hard, v),
-                         'soft_MAE': _wmean((soft_depths - T['depth_3D']).abs() / t_depth_safe, v),
-                         'mean_MAE': _wmean((comb_depth.mean(dim=1) - T['depth_3D']).abs() / t_depth_safe, v)})
+            logs.update(mae)
             if self.log_as_float:
                 vals = torch.stack([x.float() for x in logs.values()]).tolist()     # the step's single host sync
                 logs = dict(zip(logs.keys(), vals))

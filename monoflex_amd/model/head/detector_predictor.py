@@ -18,7 +18,7 @@ from ... import autograd as AG
 from ... import lib as L
 from ... import ops
 
-HM_LD = 64          # fp32 head map row: [0:3] class logits, [8:58] regression channels
+HM_LD = 64          # fp32 head map row: [0:3] class logits, [8:8+R] regression channels (R = 50 for runs/monoflex.yaml, 26..49 for a reduced head set)
 REG_OFF = 8
 
 
@@ -59,6 +59,12 @@ class _predictor(nn.Module):
         classes = len(cfg.DATASETS.DETECT_CLASSES)
         self.regression_head_cfg = cfg.MODEL.HEAD.REGRESSION_HEADS
         self.regression_channel_cfg = cfg.MODEL.HEAD.REGRESSION_CHANNELS
+        self.head_set = L.head_set(cfg)                   # refuses what the reference cannot train; R = the regression row's width
+        self.reg_width = self.head_set.R
+        if len(self.regression_head_cfg) > L.HEAD_MAX_BRANCH:
+            raise NotImplementedError("%d regression branches: the sparse head kernels take up to %d" % (len(self.regression_head_cfg), L.HEAD_MAX_BRANCH))
+        if any(sum(c) > 32 for c in self.regression_channel_cfg):
+            raise NotImplementedError("a regression branch of more than 32 channels: the sparse head kernels take up to 32 per branch")
         self.output_width = cfg.INPUT.WIDTH_TRAIN // cfg.MODEL.BACKBONE.DOWN_RATIO
         self.output_height = cfg.INPUT.HEIGHT_TRAIN // cfg.MODEL.BACKBONE.DOWN_RATIO
         self.head_conv = cfg.MODEL.HEAD.NUM_CHANNEL
@@ -153,7 +159,7 @@ class _predictor(nn.Module):
     # ---- forward ---------------------------------------------------------------------------------
     def forward_nhwc(self, features, edge_indices=None, edge_lens=None, edge_rowmap=None):
         """features (B,H,W,64) NHWC -> fp32 head map (B,H,W,64): [0:3] class logits (pre-sigmoid, after
-        edge fusion), [8:58] the 50 regression channels.  edge_indices int32 (B,L,2) (x,y), edge_lens int32 (B,)."""
+        edge fusion), [8:8+R] the R regression channels.  edge_indices int32 (B,L,2) (x,y), edge_lens int32 (B,)."""
         if self.training:
             raise RuntimeError("forward_nhwc is the fused eval path; training goes through forward_train")
         p = self._pack(ops.compute_tag(self, features.dtype))
@@ -181,11 +187,11 @@ class _predictor(nn.Module):
     def forward_train(self, features, edge_indices=None, edge_lens=None, object_rows=None, plan=None):
         """Training form (detector_predictor.py:125-169), unfused and differentiable: per branch
         conv3x3 -> ABN(batch statistics, leaky 0.01) -> one 1x1 conv over the branch's stacked heads; edge fusion
-        gathers the two trunks at the border points.  Returns (class logits (B,H,W,ncls), regression (B,H,W,50)).
+        gathers the two trunks at the border points.  Returns (class logits (B,H,W,ncls), regression (B,H,W,R)).
 
         With `object_rows` (the loss's packed object table, fp32 [N,72]) the regression branches whose activation nothing else
         reads are evaluated at the object centres only (csrc/head_sparse.hip) and the second result is the GATHERED table
-        (N,50) -- the rows select_point_of_interest would pick (layers/utils.py:120-145); the class head (dense focal loss) and
+        (N,R) -- the rows select_point_of_interest would pick (layers/utils.py:120-145); the class head (dense focal loss) and
         the 3d_offset head (edge fusion reads its trunk) keep the dense path.
 
         `plan` (`edge_plan`): the index tensors of the edge fusion that are functions of the targets alone, prepared with the batch
@@ -242,7 +248,7 @@ class _predictor(nn.Module):
             new = []
             gram_tab = None
             if gram_off:
-                # the sparse set as ONE node: the (N, 50) table of all eight regression branches at the object centres + the 3d_offset trunk's
+                # the sparse set as ONE node: the (N, R) table of all sparse regression branches at the object centres + the 3d_offset trunk's
                 # activation at the edge-sequence pixels (its edge-fusion input)
                 gram_tab, edge_rows[1 + oi] = self._gram_table(features, object_rows, sp, rowmap if fuse_nodes else None, oi)
             for bi_f, f, seq, base in ((0, feats[0], self.trunc_heatmap_conv, cls), (1 + oi, feats[1 + oi], self.trunc_offset_conv, regs[oi])):
@@ -294,11 +300,11 @@ class _predictor(nn.Module):
             return cls, gram_tab
         if gram:
             from monoflex_amd.gram_heads import gram_reg_heads
-            tab, _ = gram_reg_heads(features, rows, [e[2] for e in sp], [starts[e[0]] for e in sp], 50, [e[6] for e in sp],
+            tab, _ = gram_reg_heads(features, rows, [e[2] for e in sp], [starts[e[0]] for e in sp], self.reg_width, [e[6] for e in sp],
                                     [e[2].weight for e in sp], [e[2].bias for e in sp], [e[3] for e in sp], [e[4] for e in sp],
                                     sync=any(bool(getattr(e[2], "sync_bn", False)) for e in sp))
         else:
-            tab = AG.SparseRegHeadsFn.apply(rows, tuple(e[2] for e in sp), tuple(starts[e[0]] for e in sp), 50, tuple(e[5] for e in sp),
+            tab = AG.SparseRegHeadsFn.apply(rows, tuple(e[2] for e in sp), tuple(starts[e[0]] for e in sp), self.reg_width, tuple(e[5] for e in sp),
                                             *[e[1] for e in sp], *[e[2].weight for e in sp], *[e[2].bias for e in sp],
                                             *[e[3] for e in sp], *[e[4] for e in sp])
         bidx, cx, cy = rows[:, 57].long().clamp(0, B - 1), rows[:, 2].long().clamp(0, W - 1), rows[:, 3].long().clamp(0, H - 1)
@@ -330,18 +336,18 @@ class _predictor(nn.Module):
                 "off_cols": torch.arange(lo, lo + self.trunc_offset_conv[3].out_channels, device=rows.device)}
 
     def _gram_table(self, features, rows, sp, edge_rowmap, oi):
-        """All sparse branches in `sp` through monoflex_amd/gram_heads.py: (table (N, 50), the 3d_offset trunk's activation rows at `edge_rowmap`)."""
+        """All sparse branches in `sp` through monoflex_amd/gram_heads.py: (table (N, R), the 3d_offset trunk's activation rows at `edge_rowmap`)."""
         from monoflex_amd.gram_heads import gram_reg_heads
         starts = [sum(sum(c) for c in self.regression_channel_cfg[:i]) for i in range(len(self.regression_channel_cfg))]
         jb = [k for k, e in enumerate(sp) if e[0] == oi]
-        return gram_reg_heads(features, rows, [e[2] for e in sp], [starts[e[0]] for e in sp], 50, [e[6] for e in sp],
+        return gram_reg_heads(features, rows, [e[2] for e in sp], [starts[e[0]] for e in sp], self.reg_width, [e[6] for e in sp],
                               [e[2].weight for e in sp], [e[2].bias for e in sp], [e[3] for e in sp], [e[4] for e in sp],
                               sync=any(bool(getattr(e[2], "sync_bn", False)) for e in sp),
                               extra_branch=jb[0] if (edge_rowmap is not None and jb) else -1, extra_rows=edge_rowmap if jb else None)
 
     def forward(self, features, targets, object_rows=None):
         """Reference surface: features (B,64,H,W) (any strides) + targets -> {'cls','reg'} NCHW views.  Training with
-        `object_rows` (see forward_train): {'cls', 'reg_rows' (N,50), 'cls_logits_nhwc'} -- what the loss reads, no dense 'reg'."""
+        `object_rows` (see forward_train): {'cls', 'reg_rows' (N,R), 'cls_logits_nhwc'} -- what the loss reads, no dense 'reg'."""
         x = features.permute(0, 2, 3, 1).contiguous()
         ei, el = getattr(targets, "edge", None) or stack_edge_fields(targets, x.device)
         if self.training and object_rows is not None:
@@ -358,7 +364,7 @@ class _predictor(nn.Module):
             return {'cls': cls.permute(0, 3, 1, 2), 'reg': reg.permute(0, 3, 1, 2), 'cls_logits_nhwc': logits}
         hm = self.forward_nhwc(x, ei, el)
         cls = torch.sigmoid(hm[..., :self.num_classes]).clamp(min=1e-4, max=1 - 1e-4).permute(0, 3, 1, 2)
-        return {'cls': cls, 'reg': hm[..., REG_OFF:REG_OFF + 50].permute(0, 3, 1, 2), 'hm_nhwc': hm, 'cls_planar': self.last_cls_planar}
+        return {'cls': cls, 'reg': hm[..., REG_OFF:REG_OFF + self.reg_width].permute(0, 3, 1, 2), 'hm_nhwc': hm, 'cls_planar': self.last_cls_planar}
 
 
 class _LazyMaps(dict):

@@ -415,16 +415,18 @@ def decode_topk(hmap, ch_off, ncls, K, planar=None):
 
 
 @on_tensor_device
-def decode_boxes(hmap, reg_off, scores, index, calib, pad, img_size, threshold, depth_mode="soft", cfg=None, return_unc=False):
+def decode_boxes(hmap, reg_off, scores, index, calib, pad, img_size, threshold, depth_mode="soft", cfg=None, return_unc=False, heads=None):
     """`depth_mode`: the reference's `output_depth` name (lib.DEPTH_MODES; 'oracle' needs ground truth and is not a decode mode).
     `cfg`: a lib.DecodeCfg (lib.decode_cfg) with the head settings the model was trained with; None is the runs/monoflex.yaml decode
     (mfx_decode_boxes_mode).  `depth_mode` overrides the cfg's own output_depth.  `return_unc` (needs a cfg) appends
-    unc (B,K,2) = [estimated_depth_error, uncertainty_conf], zeros when the cfg's uncertainty_as_conf is off."""
+    unc (B,K,2) = [estimated_depth_error, uncertainty_conf], zeros when the cfg's uncertainty_as_conf is off.
+    `heads` (needs a cfg): a lib.HeadLayout (lib.HeadSet.layout()) for a head set other than the nine-key one of runs/monoflex.yaml
+    (mfx_decode_boxes_heads); unc is zero too where the set has no uncertainty head for the chosen depth."""
     _need_cuda(hmap, scores, index, calib, pad, img_size)
     if depth_mode not in L.DEPTH_MODES:
         raise ValueError("decode_boxes: output_depth %r is not one of %s" % (depth_mode, sorted(L.DEPTH_MODES)))
-    if return_unc and cfg is None:
-        raise ValueError("decode_boxes: return_unc needs a cfg (lib.decode_cfg)")
+    if (return_unc or heads is not None) and cfg is None:
+        raise ValueError("decode_boxes: return_unc / heads need a cfg (lib.decode_cfg)")
     B, H, W, ld = hmap.shape
     ncls, K = scores.shape[1], scores.shape[2]
     det = torch.empty((B, K, 14), dtype=torch.float32, device=hmap.device)
@@ -438,6 +440,11 @@ def decode_boxes(hmap, reg_off, scores, index, calib, pad, img_size, threshold, 
     c = L.DecodeCfg.from_buffer_copy(cfg)                       # (the caller's struct keeps its own output_depth)
     c.output_depth = L.DEPTH_MODES[depth_mode]
     unc = torch.empty((B, K, 2), dtype=torch.float32, device=hmap.device) if return_unc else None
+    if heads is not None:
+        L.check(L.load().mfx_decode_boxes_heads(_ptr(hmap), ld, reg_off, _ptr(scores), _ptr(index), ncls, B, H, W, K, _ptr(calib),
+                                                _ptr(pad), _ptr(img_size), ctypes.c_float(threshold), ctypes.byref(c), ctypes.byref(heads),
+                                                _ptr(det), _ptr(topk), _ptr(valid), _ptr(unc), _stream()), "mfx_decode_boxes_heads")
+        return (det, topk, valid, unc) if return_unc else (det, topk, valid)
     L.check(L.load().mfx_decode_boxes_cfg(_ptr(hmap), ld, reg_off, _ptr(scores), _ptr(index), ncls, B, H, W, K, _ptr(calib),
                                           _ptr(pad), _ptr(img_size), ctypes.c_float(threshold), ctypes.byref(c), _ptr(det), _ptr(topk),
                                           _ptr(valid), _ptr(unc), _stream()), "mfx_decode_boxes_cfg")
