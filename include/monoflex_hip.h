@@ -622,6 +622,29 @@ int mfx_object_loss_backward_width(const float* G, const float* gout_terms, cons
  * One lane per pair, one launch on `stream`, nothing allocated, no synchronisation; N == 0 returns MFX_OK without a launch. */
 int mfx_box3d_iou_pairs(const float* boxes_a, const float* boxes_b, int N, int form, float* iou, void* stream);
 
+/* Validation diagnostics at the ground-truth centres (csrc/eval_diag.hip, csrc/eval_diag_math.h; reference PostProcessor.evaluate_3D_depths,
+ * model/head/detector_infer.py:280-359 = TEST.EVAL_DEPTH, and evaluate_3D_detection, :361-452 = TEST.EVAL_DIS_IOUS).  One lane per (image,
+ * object slot) reads the regression row at the object's target centre, hmap[(b*H*W + cy*W + cx)*ld + reg_off ...], and decodes it with the
+ * target class, the image's own calib / pad and the head settings of `cfg` / `heads` (host pointers, copied by value into the launch).
+ *   gt_rows  : fp32 [B][M][16] = reg_mask, cls_id, cx, cy, offset_3D x, y, location X, Y, Z (Y = the box centre), dimensions l, h, w, roty,
+ *              three spare.  reg_mask == 0: the slot writes zeros to every output and reads nothing from hmap.  A valid slot whose centre
+ *              lies outside the map, or whose class is not 0..2, reads nothing either and writes NaN.
+ *   want     : bit 0 = depth errors, bit 1 = boxes / IoUs (1..3).  An output that is not wanted may be NULL.
+ *   depth_err: fp32 [B][M][13] = direct, direct_sigma, keypoint_center, keypoint_02, keypoint_13, keypoint_center_sigma, keypoint_02_sigma,
+ *              keypoint_13_sigma, sigma_min, sigma_weighted, mean, min, target: |estimate - Z_target| for the error keys, the values themselves
+ *              for the sigma keys and `target`.  Needs depth_uncertainty, corner_offset and corner_uncertainty in `heads`.
+ *   iou      : fp32 [B][M][5] = pred_IoU, offset_IoU, depth_IoU, dims_IoU, orien_IoU: mfx_box3d_iou_pairs' form-0 arithmetic of boxes 0, 2, 3, 4,
+ *              5 below with box 1.
+ *   boxes    : optional fp32 [B][M][6][7] rows (x, y, z, l, h, w, ry): 0 predicted (depth by cfg->output_depth, as mfx_decode_boxes_heads
+ *              decodes that pixel under that class, Y without the half height), 1 target, 2 predicted offset, 3 predicted depth, 4 predicted
+ *              dimensions, 5 predicted orientation -- the rest of 2..5 is ground truth.  The reference builds these under 'direct' only; the
+ *              other MFX_DEPTH_* modes follow mfx_decode_boxes_heads' combination and head-set rule.
+ * One launch of ceil(B*M/64) 64-lane workgroups on `stream`, nothing allocated, no synchronisation; B*M == 0 returns MFX_OK without a launch. */
+enum { MFX_EVAL_GT_ROW = 16, MFX_EVAL_DEPTH_KEYS = 13, MFX_EVAL_IOU_KEYS = 5, MFX_EVAL_BOXES = 6 };
+int mfx_eval_diagnostics(const float* hmap, int ld, int reg_off, const float* gt_rows, int B, int M, int H, int W,
+                         const float* calib, const int32_t* pad, const mfx_decode_cfg* cfg, const mfx_head_layout* heads,
+                         int want, float* depth_err, float* iou, float* boxes, void* stream);
+
 /* Regression branches of the training step evaluated at the object centres only (csrc/head_sparse.hip; reference
  * model/head/detector_predictor.py:125-169 + the gather of model/layers/utils.py:120-145).  Per branch i: y[i] = the dense trunk
  * conv output (B,H,W,256) in `dtype`, mean/rstd = its batch statistics, gamma/beta = the ABN parameters, w2 (k,256) / b2 (k) = the

@@ -1,17 +1,44 @@
 """Evaluation loop (reference engine/inference.py:17-126): run the detector over a loader, write one KITTI result file per
 image, score them.  Batches of any size are accepted (the reference is batch-1 only); the per-image (N,14) rows come back
-from the device once per batch.  The disentangled-IoU statistics of the reference (`eval_score_iou`) are not produced."""
+from the device once per batch.  TEST.EVAL_DIS_IOUS / TEST.EVAL_DEPTH (the reference's disentangled 3D IoUs, engine/inference.py:45-63,92-93,
+and per-object depth errors) are computed on the device at the labelled centres and averaged here; the score-versus-IoU plots of
+`--eval_score_iou` and `--vis` are not produced."""
 import logging
 import os
 import time
 
 import torch
 
+from .. import ops
 from ..data.evaluation import evaluate_python, generate_kitti_3d_detection
 from ..parallel import barrier
 
 
-def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, overlap=True):
+class _DiagnosticSums:
+    """Host-side sums of the per-object diagnostics over a pass -> the means `compute_on_dataset(diagnostics=...)` reports."""
+
+    def __init__(self):
+        self.sums = {"depth_errors": None, "dis_ious": None}
+        self.objects = 0
+
+    def add(self, depth_err, iou, mask):
+        """Fixed-shape host tables (B,M,13) / (B,M,5) (None when not computed) and reg_mask (B,M); float64 sums."""
+        keep = mask.reshape(-1) != 0
+        self.objects += int(keep.sum())
+        for name, t in (("depth_errors", depth_err), ("dis_ious", iou)):
+            if t is not None:
+                part = t.reshape(-1, t.shape[-1])[keep].double().sum(dim=0)
+                self.sums[name] = part if self.sums[name] is None else self.sums[name] + part
+
+    def write(self, out):
+        n = self.objects
+        for name, keys in (("dis_ious", ops.EVAL_IOU_KEYS), ("depth_errors", ops.EVAL_DEPTH_KEYS)):
+            s = self.sums[name]
+            out[name] = {} if s is None else {k: (float(s[i]) / n if n else float("nan")) for i, k in enumerate(keys)}
+        out["objects"] = n
+
+
+def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, overlap=True, diagnostics=None):
     """Returns the number of images processed; `timer`, if given, is a dict that receives the seconds spent in the model (launches + waits).
     `overlap` (default, CUDA only): ONE batch stays in flight -- the fixed-size (B,50,14) rows and validity flags of batch k are copied to
     pinned memory behind an event, batch k+1 is launched, and only then does the host wait for batch k's event and write its files
@@ -24,12 +51,22 @@ def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, o
     if getattr(getattr(getattr(model, "heads", None), "post_processor", None), "output_depth", None) == "oracle":
         overlap = False                                            # reads each image's ground truth on the host (PostProcessor.decode_oracle)
     pending = None
+    post = getattr(getattr(model, "heads", None), "post_processor", None)
+    want = int(getattr(post, "diagnostics_wanted", 0))
+    sums = _DiagnosticSums()
+
+    def pinned(t):
+        h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+        h.copy_(t, non_blocking=True)
+        return h
 
     def finish(p):
-        ev, rows_h, valid_h, ids = p
+        ev, rows_h, valid_h, ids, diag_h = p
         ev.synchronize()
         for b, image_id in enumerate(ids):
             generate_kitti_3d_detection(rows_h[b][valid_h[b].bool()], os.path.join(predict_folder, image_id + ".txt"))
+        if diag_h is not None:
+            sums.add(*diag_h)
         return len(ids)
 
     with torch.no_grad():
@@ -40,17 +77,27 @@ def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, o
             t0 = time.perf_counter()
             if overlap:
                 tensors = images.tensors if hasattr(images, "tensors") else images
-                det, _, valid, _ = model.detect_device(tensors, *model.device_targets(targets, dev))
+                dt = model.device_targets(targets, dev)
+                det, _, valid, hm = model.detect_device(tensors, *dt)
                 rows_h = torch.empty(det.shape, dtype=det.dtype, pin_memory=True)
                 valid_h = torch.empty(valid.shape, dtype=valid.dtype, pin_memory=True)
                 rows_h.copy_(det, non_blocking=True)
                 valid_h.copy_(valid, non_blocking=True)
+                diag_h = None
+                if want:        # the diagnostics kernel, the ~16 small torch launches that stack its (B,M,16) table (a fill, casts, slice copies) and up to
+                                # three more fixed-shape copies to pinned memory, all behind the same event: no synchronisation is added
+                    fields = batch.get("fields")                       # (the test split's targets carry no labels: ValueError, as forward)
+                    labelled = fields is not None and all(t.has_field("reg_mask") for t in targets)
+                    gt_rows = ops.eval_diag_rows(fields if labelled else targets, dev)
+                    depth_err, iou = model.diagnose_device(hm, gt_rows, dt[2], dt[3])
+                    diag_h = (None if depth_err is None else pinned(depth_err), None if iou is None else pinned(iou),
+                              pinned(gt_rows[..., 0].contiguous()))
                 ev = torch.cuda.Event()
                 ev.record()
                 busy += time.perf_counter() - t0
                 if pending is not None:
                     n += finish(pending)
-                pending = (ev, rows_h, valid_h, list(image_ids))
+                pending = (ev, rows_h, valid_h, list(image_ids), diag_h)
                 continue
             output, eval_utils, _ = model(images, targets)
             outputs = [output] if torch.is_tensor(output) else list(output)
@@ -59,6 +106,12 @@ def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, o
             for image_id, rows in zip(image_ids, outputs):
                 generate_kitti_3d_detection(rows, os.path.join(predict_folder, image_id + ".txt"))
             n += len(outputs)
+            if want:                                                   # the valid objects' values, (image, slot) order (PostProcessor.forward)
+                de, di = eval_utils["depth_errors"], eval_utils["dis_ious"]
+                stack = lambda d, keys: None if d is None else torch.stack([d[k] for k in keys], dim=1).cpu()
+                de, di = stack(de, ops.EVAL_DEPTH_KEYS), stack(di, ops.EVAL_IOU_KEYS)
+                count = (de if de is not None else di).shape[0]
+                sums.add(de, di, torch.ones(count))
         if pending is not None:
             t0 = time.perf_counter()
             pending[0].synchronize()
@@ -66,12 +119,17 @@ def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, o
             n += finish(pending)
     if timer is not None:
         timer["inference_seconds"] = timer.get("inference_seconds", 0.0) + busy
+    if diagnostics is not None:
+        sums.write(diagnostics)
     return n
 
 
 def inference(model, data_loader, dataset_name, eval_types=("detections",), device="cuda", output_folder=None, metrics=("R40",)):
     """-> (ret_dicts, result text of the last metric, dis_ious) on rank 0, (None, None, None) elsewhere
-    (engine/inference.py:66-126). Every rank writes the result files of its shard into `<output_folder>/data`."""
+    (engine/inference.py:66-126). Every rank writes the result files of its shard into `<output_folder>/data`.
+    dis_ious: {key: mean 3D IoU} of the five disentangled IoUs under TEST.EVAL_DIS_IOUS, {} without it; logged as the reference's
+    "<key>, MEAN IOU = ..." lines, and the depth errors of TEST.EVAL_DEPTH as one line per key.  The means are rank-local, like the
+    reference's: each rank averages (and rank 0 returns) the objects of its own shard; they are not reduced across ranks."""
     import torch.distributed as dist
     logger = logging.getLogger("monoflex.inference")
     dataset = data_loader.dataset
@@ -79,8 +137,13 @@ def inference(model, data_loader, dataset_name, eval_types=("detections",), devi
     os.makedirs(predict_folder, exist_ok=True)
     timer = {}
     t0 = time.perf_counter()
-    n = compute_on_dataset(model, data_loader, torch.device(device), predict_folder, timer)
+    diagnostics = {}
+    n = compute_on_dataset(model, data_loader, torch.device(device), predict_folder, timer, diagnostics=diagnostics)
     barrier()
+    for key, value in diagnostics["dis_ious"].items():
+        logger.info("%s, MEAN IOU = %.4f", key, value)
+    for key, value in diagnostics["depth_errors"].items():
+        logger.info("depth %s, MEAN = %.4f", key, value)
     logger.info("%s: %d images in %.2f s (%.4f s / img in the model)", dataset_name, n, time.perf_counter() - t0,
                 timer["inference_seconds"] / max(n, 1))
     if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
@@ -92,7 +155,7 @@ def inference(model, data_loader, dataset_name, eval_types=("detections",), devi
                                            device=device)
         logger.info("metric = %s\n%s", metric, result)
         ret_dicts.append(ret_dict)
-    return ret_dicts, result, {}
+    return ret_dicts, result, diagnostics["dis_ious"]
 
 
 EVAL_DEPTH_METHODS = ("oracle", "hard", "soft", "mean", "direct", "keypoints_center", "keypoints_02", "keypoints_13")   # engine/inference.py:154

@@ -210,6 +210,7 @@ SYMBOLS = {
     "mfx_object_loss_backward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "mfx_object_loss_backward_width": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "mfx_box3d_iou_pairs": (_I, [_P, _P, _I, _I, _P, _P]),
+    "mfx_eval_diagnostics": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, ctypes.POINTER(DecodeCfg), ctypes.POINTER(HeadLayout), _I, _P, _P, _P, _P]),
     "mfx_kitti_encode_targets": (_I, [ctypes.POINTER(KittiDesc), _P]),
     "mfx_kitti_encode_targets_views": (_I, [ctypes.POINTER(KittiDesc), _P, _P]),
     "mfx_kitti_preprocess_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.POINTER(c_float), ctypes.POINTER(c_float), _P]),

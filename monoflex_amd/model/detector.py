@@ -55,6 +55,10 @@ class KeypointDetector(nn.Module):
         det, topk, valid = self.heads.post_processor.decode_device(hm, pad, calib, size, self.heads.predictor.last_cls_planar)
         return det, topk, valid, hm
 
+    def diagnose_device(self, hm, gt_rows, pad, calib):
+        """TEST.EVAL_DEPTH / TEST.EVAL_DIS_IOUS on the `hm` detect_device returned: (depth_err (B,M,13), iou (B,M,5)), None where the flag is off."""
+        return self.heads.post_processor.diagnose_device(hm, gt_rows, pad, calib)
+
     def forward_train_maps(self, images, edge_indices, edge_lens):
         """Training-mode network: (B,3,H,W) images -> (class logits (B,h,w,ncls), regression (B,h,w,R)), NHWC,
         differentiable (HIP forward + backward kernels; BN on batch statistics)."""

@@ -60,6 +60,15 @@ class PostProcessor(nn.Module):
         self.decode_cfg = L.decode_cfg(s, self.uncertainty_as_conf)
         self.head_layout = hs.layout()
         self.reg_width = hs.R
+        # TEST.EVAL_DEPTH / TEST.EVAL_DIS_IOUS (detector_infer.py:37-38,86-89): the ground-truth diagnostics of a validation pass, evaluated on
+        # the device at the labelled centres (ops.eval_diagnostics).  What the head set cannot serve is refused here, as above.
+        self.eval_depth, self.eval_dis_iou = bool(cfg.TEST.EVAL_DEPTH), bool(cfg.TEST.EVAL_DIS_IOUS)
+        if self.eval_depth and not hs.full:
+            raise NotImplementedError("TEST.EVAL_DEPTH with the %s: the depth errors read depth_uncertainty, corner_offset and corner_uncertainty "
+                                      "(detector_infer.py:296-300)" % hs.describe())
+        if self.eval_dis_iou and self.output_depth == 'oracle':
+            raise NotImplementedError("TEST.EVAL_DIS_IOUS with OUTPUT_DEPTH 'oracle': the disentangled boxes take the depth of one decode mode "
+                                      "(%s)" % ", ".join(L.DEPTH_MODES))
 
     @staticmethod
     def prepare_targets(targets, device):
@@ -81,9 +90,41 @@ class PostProcessor(nn.Module):
         return ops.decode_boxes(hm, REG_OFF, scores, index, calib, pad, size, float(self.det_threshold), depth_mode=self.output_depth,
                                 cfg=self.decode_cfg, return_unc=return_unc, heads=self.head_layout)
 
+    @property
+    def diagnostics_wanted(self):
+        """mfx_eval_diagnostics' `want`: bit 0 = TEST.EVAL_DEPTH, bit 1 = TEST.EVAL_DIS_IOUS."""
+        return (1 if self.eval_depth else 0) | (2 if self.eval_dis_iou else 0)
+
+    def diagnose_device(self, hm, gt_rows, pad, calib):
+        """hm fp32 (B,H,W,64), gt_rows (B,M,16) (ops.eval_diag_rows) -> (depth_err (B,M,13) or None, iou (B,M,5) or None): the fixed-shape
+        tables of the flags that are on, zeros in the empty slots; one launch, no host synchronisation."""
+        want = self.diagnostics_wanted
+        if not want:
+            return None, None
+        # (`output_depth` is read at every call, as decode_device does)
+        if want & 2:
+            if self.output_depth == 'oracle':
+                raise NotImplementedError("TEST.EVAL_DIS_IOUS with output_depth 'oracle'")
+            self.head_set.check_output_depth(self.output_depth)
+        c = L.DecodeCfg.from_buffer_copy(self.decode_cfg)
+        c.output_depth = L.DEPTH_MODES[self.output_depth] if want & 2 else L.DEPTH_MODES['direct']
+        return ops.eval_diagnostics(hm, REG_OFF, gt_rows, calib, pad, c, self.head_layout, want=want)
+
+    @staticmethod
+    def diagnostics_tables(depth_err, iou, mask):
+        """The fixed-shape tables -> the reference's dicts {key: 1-D tensor over the valid objects in (image, slot) order}
+        (detector_infer.py:341-357,450); None for a table that was not computed."""
+        keep = mask.reshape(-1).bool()
+        rows = lambda t, keys: None if t is None else {k: t.reshape(-1, len(keys))[keep, i] for i, k in enumerate(keys)}
+        return rows(depth_err, ops.EVAL_DEPTH_KEYS), rows(iou, ops.EVAL_IOU_KEYS)
+
     def forward(self, predictions, targets, features=None, test=False, refine_module=None):
         hm = predictions['hm_nhwc']
         pad, calib, size = self.prepare_targets(targets, hm.device)
+        depth_errors = dis_ious = None
+        if self.diagnostics_wanted:
+            gt_rows = ops.eval_diag_rows(targets, hm.device)            # ValueError on targets without labels (the `test` split)
+            depth_errors, dis_ious = self.diagnostics_tables(*self.diagnose_device(hm, gt_rows, pad, calib), gt_rows[..., 0])
         if self.output_depth == 'oracle':
             det, topk, valid, unc = self.decode_oracle(hm, pad, calib, size, predictions.get('cls_planar'), targets)
         else:
@@ -97,7 +138,7 @@ class PostProcessor(nn.Module):
         report = self.uncertainty_as_conf and self.head_set.has_depth_error(self.output_depth)
         depth_error = one([unc[b][keep[b], 0] for b in range(det.shape[0])]) if report else None
         unc_conf = one([unc[b][keep[b], 1] for b in range(det.shape[0])]) if report else None
-        eval_utils = {'dis_ious': None, 'depth_errors': None, 'vis_scores': one(vis_scores), 'uncertainty_conf': unc_conf,
+        eval_utils = {'dis_ious': dis_ious, 'depth_errors': depth_errors, 'vis_scores': one(vis_scores), 'uncertainty_conf': unc_conf,
                       'estimated_depth_error': depth_error, 'topk': topk, 'valid': valid, 'det_all': det}
         visualize_preds = {'heat_map': predictions['cls']}
         result = results[0] if len(results) == 1 else results

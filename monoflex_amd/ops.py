@@ -613,3 +613,64 @@ def box3d_iou(a, b):
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
     L.check(L.load().mfx_box3d_iou_pairs(_ptr(x), _ptr(y), x.shape[0], 0 if x.dim() == 2 else 1, _ptr(out), _stream()), "mfx_box3d_iou_pairs")
     return out
+
+
+# ---- validation diagnostics at the ground-truth centres (TEST.EVAL_DEPTH / TEST.EVAL_DIS_IOUS) ------------------------------------------
+EVAL_DEPTH_KEYS = ("direct", "direct_sigma", "keypoint_center", "keypoint_02", "keypoint_13", "keypoint_center_sigma", "keypoint_02_sigma",
+                   "keypoint_13_sigma", "sigma_min", "sigma_weighted", "mean", "min", "target")       # detector_infer.py:341-357, mfx_eval_diagnostics' columns
+EVAL_IOU_KEYS = ("pred_IoU", "offset_IoU", "depth_IoU", "dims_IoU", "orien_IoU")                       # detector_infer.py:450
+EVAL_GT_FIELDS = ("reg_mask", "cls_ids", "target_centers", "offset_3D", "locations", "dimensions", "rotys")
+EVAL_GT_ROW = 16
+
+
+def eval_diag_rows(source, device):
+    """The ground-truth table of mfx_eval_diagnostics, fp32 (B, M, 16) on `device`: reg_mask, cls_id, cx, cy, offset_3D x, y, location X, Y, Z,
+    dimensions l, h, w, roty, three spare.  `source`: the loader's batch-stacked `fields` dict, or the per-image ParamsLists (stacked here).
+    Targets without the ground-truth fields (the `test` split) raise ValueError."""
+    if isinstance(source, dict):
+        missing = [k for k in EVAL_GT_FIELDS if k not in source]
+        get = lambda k: torch.as_tensor(source[k])
+    else:
+        source = list(source)
+        missing = [k for k in EVAL_GT_FIELDS if not all(t.has_field(k) for t in source)]
+        get = lambda k: torch.stack([torch.as_tensor(t.get_field(k)) for t in source])
+    if missing:
+        raise ValueError("TEST.EVAL_DEPTH / TEST.EVAL_DIS_IOUS read the ground truth of every image, and these targets have no %s "
+                         "(the `test` split has no labels: evaluate a split that has)" % ", ".join(missing))
+    mask = get("reg_mask")
+    B, M = mask.shape[:2]
+    f = lambda k, w: get(k).to(device=device, dtype=torch.float32).reshape(B, M, w)
+    rows = torch.zeros((B, M, EVAL_GT_ROW), dtype=torch.float32, device=device)
+    col = 0
+    for k, w in (("reg_mask", 1), ("cls_ids", 1), ("target_centers", 2), ("offset_3D", 2), ("locations", 3), ("dimensions", 3), ("rotys", 1)):
+        rows[:, :, col:col + w] = f(k, w)
+        col += w
+    return rows
+
+
+@on_tensor_device
+def eval_diagnostics(hmap, reg_off, gt_rows, calib, pad, cfg, heads, want=3, return_boxes=False):
+    """mfx_eval_diagnostics: the reference's evaluate_3D_depths / evaluate_3D_detection at every object slot of `gt_rows` (eval_diag_rows).
+    hmap fp32 (B, H, W, ld); cfg / heads: lib.DecodeCfg (its output_depth decides the predicted depth of the boxes) / lib.HeadLayout.
+    -> (depth_err (B, M, 13) or None, iou (B, M, 5) or None[, boxes (B, M, 6, 7)]), columns EVAL_DEPTH_KEYS / EVAL_IOU_KEYS, zeros in the
+    slots whose reg_mask is 0.  One launch on the current stream, no host synchronisation, fixed shapes."""
+    _need_cuda(hmap, gt_rows, calib, pad)
+    if hmap.dtype != torch.float32 or gt_rows.dtype != torch.float32 or calib.dtype != torch.float32 or pad.dtype != torch.int32:
+        raise TypeError("eval_diagnostics: hmap, gt_rows and calib are float32, pad is int32")
+    B, H, W, ld = hmap.shape
+    if gt_rows.dim() != 3 or gt_rows.shape[0] != B or gt_rows.shape[2] != EVAL_GT_ROW or tuple(calib.shape) != (B, 6) or tuple(pad.shape) != (B, 2):
+        raise RuntimeError("eval_diagnostics: gt_rows (B, M, 16), calib (B, 6), pad (B, 2) for hmap (B, H, W, ld); got %s, %s, %s, %s"
+                           % (tuple(gt_rows.shape), tuple(calib.shape), tuple(pad.shape), tuple(hmap.shape)))
+    if not (hmap.is_contiguous() and gt_rows.is_contiguous() and calib.is_contiguous() and pad.is_contiguous()):
+        raise RuntimeError("eval_diagnostics: operands must be contiguous")
+    if return_boxes and not want & 2:
+        raise ValueError("eval_diagnostics: the boxes come with the IoUs (want bit 1)")
+    M = gt_rows.shape[1]
+    dev = hmap.device
+    depth_err = torch.empty((B, M, len(EVAL_DEPTH_KEYS)), dtype=torch.float32, device=dev) if want & 1 else None
+    iou = torch.empty((B, M, len(EVAL_IOU_KEYS)), dtype=torch.float32, device=dev) if want & 2 else None
+    boxes = torch.empty((B, M, 6, 7), dtype=torch.float32, device=dev) if return_boxes else None
+    L.check(L.load().mfx_eval_diagnostics(_ptr(hmap), ld, reg_off, _ptr(gt_rows), B, M, H, W, _ptr(calib), _ptr(pad), ctypes.byref(cfg),
+                                          ctypes.byref(heads), int(want), _ptr(depth_err), _ptr(iou), _ptr(boxes), _stream()),
+            "mfx_eval_diagnostics")
+    return (depth_err, iou, boxes) if return_boxes else (depth_err, iou)

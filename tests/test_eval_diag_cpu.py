@@ -1,0 +1,487 @@
+"""Validation diagnostics (TEST.EVAL_DEPTH / TEST.EVAL_DIS_IOUS; reference PostProcessor.evaluate_3D_depths / evaluate_3D_detection,
+model/head/detector_infer.py:280-452) without a GPU: the test inputs' own properties, the float64 restatement of tests/eval_diag_ref.py
+against the reference's recorded results (tests/golden/eval_diag.npz), the kernel arithmetic of csrc/eval_diag_math.h compiled for the host
+against both, and the Python surface (refusals, aggregation, log lines).
+
+Bounds: the reference's own float32 error against the restatement, measured here per depth-error key and per box column
+(eval_diag_ref.YARDSTICK_*), times BOUND_FACTOR (4) -- for the reference's recording, the host build and (tests/test_gpu_eval_diag.py) the
+device alike.  IoUs are compared with the float64 IoU of the very boxes the arithmetic produced, at the IoU operator's bound."""
+import ctypes
+import logging
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from monoflex_amd import lib as L                                  # noqa: E402
+from monoflex_amd import ops                                       # noqa: E402
+from tests import decode_cases as C                                # noqa: E402
+from tests import decode_ref as D                                  # noqa: E402
+from tests import eval_diag_cases as E                             # noqa: E402
+from tests import eval_diag_ref as R                               # noqa: E402
+from tests import head_sets_cases as HC                            # noqa: E402
+
+GOLD = E.golden()
+BIG = ["b4_m70", "b4_m70_direct", "b3_m70_ld50"]              # the cases with at least E.SHARE_MIN_ROWS valid objects
+
+
+# ---- the inputs ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(E.CASES))
+def test_case_shapes_and_near_rows(name):
+    d = E.case_inputs(name)
+    c = E.CASES[name]
+    gt = d["gt_rows"]
+    assert gt.shape == (len(c["images"]), c["M"], 16) and d["hmap"].shape == (len(c["images"]), E.H, E.W, c["ld"])
+    for mode in D.MODES:
+        ref = E.run_ref(d, mode, with_iou=False)
+        assert R.near_share(ref, mode) <= R.NEAR_CAP, (name, mode, R.near_share(ref, mode))
+
+
+def test_cases_cover_the_shapes():
+    cs = E.CASES.values()
+    assert {len(c["images"]) for c in cs} == {1, 3, 4} and {c["M"] for c in cs} == {1, 40, 70}
+    assert {(c["ld"], c["reg_off"]) for c in cs} == {(64, 8), (50, 0), (72, 13)}
+    some = E.case_inputs("b3_m40")
+    valid = some["gt_rows"][..., 0] != 0
+    assert not valid[1].any() and not valid[0, 0] and valid[0].any() and 0 < valid[2].sum() < 40          # an empty image, holes, first valid slot != 0
+    g = some["gt_rows"][0]
+    assert valid[0, 5] and valid[0, 6] and (g[5, 2:4] == g[6, 2:4]).all() and g[5, 1] != g[6, 1]           # two objects on one pixel
+    assert 70 * 4 > 4 * 64                                                                                # more than one workgroup, plus a tail
+
+
+@pytest.mark.parametrize("name", BIG)
+def test_case_shares_and_census(name):
+    """From the float64 restatement alone: the IoU spread, the objects at IoU 0 and the identical ones, and every branch of the decode census
+    (tests/decode_cases.py) among the rows at the labelled centres."""
+    d = E.case_inputs(name)
+    ref = E.run_ref(d)
+    assert ref["valid"].sum() >= E.SHARE_MIN_ROWS
+    s = E.shares(d, ref)
+    print("\n%s (%s), %d objects\n" % (name, d["mode"], ref["valid"].sum()) + "\n".join("  %-46s %5.1f %%" % (k, 100 * v) for k, v in s.items()))
+    for k in R.IOU_KEYS:
+        assert s["%s in (0.05, 0.95)" % k] >= 0.40, (k, s)
+    assert s["pred_IoU == 0"] >= 0.03 and s["offset_IoU == 0"] >= 0.03 and s["depth_IoU == 0"] >= 0.03, s
+    assert s["identical objects"] >= 0.03 and s["identical objects with every IoU > 0.999"] == 1.0, s
+    # the decode census over the valid objects' rows: the same pixels under the same classes through tests/decode_ref.py
+    scores, index = E.census_lists(d)
+    dr = D.decode_boxes(d["hmap"], d["reg_off"], scores, index, d["calib"], d["pad"], np.array(C.IMAGES[d["images"][0]]["size"]), C.THRESHOLD, d["mode"])
+    v = ref["valid"]
+    flat = {k: (a[v][None] if a.shape[:2] == v.shape else a[:1]) for k, a in dr.items()}
+    cen = C.census(flat, d["mode"])
+    print(C.format_census(cen))
+    # the census's own thresholds, both sides, as tests/test_decode_ref_cpu.py asserts them: every branch is taken by at least `taken` and
+    # missed by at least `missed` of the objects (for "below the clamp" / "clear of every side" the miss IS the clamp being reached)
+    for k, (share, taken, missed) in cen.items():
+        assert share >= taken and 1 - share >= missed, (name, k, share, taken, missed)
+
+
+# ---- the restatement against the reference's recording ------------------------------------------------------------------------------------
+def golden_errors():
+    """Worst error of the recording against the restatement -> ((13,), (7,))."""
+    depth, box = np.zeros(13), np.zeros(7)
+    for mode in ("soft", "direct"):
+        d, de, bx = E.golden_tables(mode)
+        ref = E.run_ref(d, mode, with_iou=False)
+        depth = np.maximum(depth, R.depth_errors_err(de, ref, mode))
+        if bx is not None:
+            box = np.maximum(box, R.boxes_err(bx, ref, mode))
+    return depth, box
+
+
+def test_golden_yardsticks():
+    assert tuple(GOLD["depth_keys"]) == R.DEPTH_KEYS and tuple(GOLD["box_names"]) == R.BOX_NAMES
+    assert "no runnable reference" in str(GOLD["meta"])
+    for k, v in E.GOLDEN.items():
+        assert np.array_equal(GOLD[k], np.array(v)), k
+    depth, box = golden_errors()
+    print("\nreference float32 vs restatement:\n  depth errors: %s\n  boxes: %s" % (R.format_depth(depth), R.format_box(box)))
+    assert (depth <= R.depth_bounds()).all(), R.format_depth(depth)
+    assert (box <= R.box_bounds()).all(), R.format_box(box)
+    # the recorded yardsticks are what is measured, not a loose cover: none exceeds 2x today's figure (0 stays 0)
+    assert (np.array([R.YARDSTICK_DEPTH[k] for k in R.DEPTH_KEYS]) <= 2 * depth + 1e-12).all()
+    assert (np.array([R.YARDSTICK_BOX[k] for k in R.BOX_COLUMNS]) <= 2 * box + 1e-12).all()
+
+
+# ---- the kernel arithmetic, compiled for the host -----------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("shim") / "libeval_diag_shim.so")
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so,
+                        os.path.join(ROOT, "tests", "shim", "eval_diag_host.cpp")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    lib = ctypes.CDLL(so)
+    P, I = ctypes.c_void_p, ctypes.c_int
+    lib.shim_eval_diagnostics.argtypes = [P, I, I, P, I, I, I, I, P, P, ctypes.POINTER(L.DecodeCfg), ctypes.POINTER(L.HeadLayout), I, P, P, P, ctypes.c_char_p]
+    lib.shim_eval_diagnostics.restype = I
+
+    def run(d, mode, want=3, cfg=None, heads=None, hmap=None, gt_rows=None):
+        hmap = np.ascontiguousarray(d["hmap"] if hmap is None else hmap, dtype=np.float32)
+        gt = np.ascontiguousarray(d["gt_rows"] if gt_rows is None else gt_rows, dtype=np.float32)
+        calib, pad = np.ascontiguousarray(d["calib"], dtype=np.float32), np.ascontiguousarray(d["pad"], dtype=np.int32)
+        B, H, W, ld = hmap.shape
+        M = gt.shape[1]
+        poison = lambda *shape: np.full(shape, 7.75e8, dtype=np.float32)
+        de, iou, bx = poison(B, M, 13), poison(B, M, 5), poison(B, M, 6, 7)
+        why = ctypes.create_string_buffer(160)
+        cfg = E.yaml_cfg(mode) if cfg is None else cfg
+        heads = E.full_layout() if heads is None else heads
+        rc = lib.shim_eval_diagnostics(hmap.ctypes.data, ld, d["reg_off"], gt.ctypes.data, B, M, H, W, calib.ctypes.data, pad.ctypes.data,
+                                       ctypes.byref(cfg), ctypes.byref(heads), want, de.ctypes.data, iou.ctypes.data,
+                                       bx.ctypes.data if want & 2 else None, why)
+        if rc:
+            raise ValueError(why.value.decode())
+        return de, iou, bx
+    return run
+
+
+def test_host_math_against_golden(shim):
+    for mode in ("soft", "direct"):
+        d, gde, gbx = E.golden_tables(mode)
+        de, iou, bx = shim(d, mode)
+        ref = dict(E.run_ref(d, mode, with_iou=False), depth_err=gde)
+        if gbx is not None:
+            ref["boxes"] = gbx
+            E.check_against(de, iou, bx, ref, mode, "golden " + mode)
+        else:
+            E.check_against(de, None, None, ref, mode, "golden " + mode)
+
+
+@pytest.mark.parametrize("name", list(E.CASES))
+def test_host_math_against_restatement(shim, name):
+    d = E.case_inputs(name)
+    for mode in D.MODES:
+        de, iou, bx = shim(d, mode)
+        E.check_against(de, iou, bx, E.run_ref(d, mode, with_iou=False), mode, "%s %s" % (name, mode))
+
+
+def test_host_math_want_bits(shim):
+    d = E.case_inputs("b3_m40")
+    de3, iou3, _ = shim(d, "soft", want=3)
+    de1, iou1, _ = shim(d, "soft", want=1)
+    de2, iou2, _ = shim(d, "soft", want=2)
+    assert np.array_equal(de1, de3) and np.array_equal(iou2, iou3)
+    assert (iou1 == np.float32(7.75e8)).all() and (de2 == np.float32(7.75e8)).all()                       # what is not wanted is not written
+
+
+@pytest.mark.parametrize("name", ["b4_m70", "b3_m70_ld50", "b4_m40_ld72"])
+def test_pred_box_is_the_decode_row(shim, name):
+    """Box 0 is what the box decode gives for the same pixel under the same class (tests/decode_ref.py, the restatement the decode kernel is
+    pinned to): X, Z, the dimensions and ry at the decode's own bounds; the decode's Y is the bottom centre, box 0's the box centre."""
+    d = E.case_inputs(name)
+    scores, index = E.census_lists(d)
+    v = d["gt_rows"][..., 0] != 0
+    b = D.bounds()
+    col = {c: i for i, c in enumerate(D.COLUMNS)}
+    for mode in D.MODES:
+        _, _, bx = shim(d, mode)
+        dr = D.decode_boxes(d["hmap"], d["reg_off"], scores, index, d["calib"], d["pad"], np.array([160, 96]), C.THRESHOLD, mode)
+        det, near = dr["det"], D.near_rows(dr, mode)
+        assert (det[..., 0][v] == d["gt_rows"][..., 1][v]).all()                                          # row j is slot j under its class
+        rel = lambda got, want: np.abs(got - want) / np.maximum(1.0, np.abs(want))
+        use = v & ~near
+        for mine, theirs in ((0, "X"), (2, "Z"), (3, "l"), (4, "h"), (5, "w")):
+            assert (rel(bx[..., 0, mine], det[..., col[theirs]])[use] <= b[col[theirs]]).all(), (mode, theirs)
+        ry = np.abs(bx[..., 0, 6] - det[..., 12])
+        ry = np.minimum(ry, np.abs(ry - 2 * np.pi)) / np.maximum(1.0, np.abs(det[..., 12]))
+        assert (ry[use] <= b[12]).all(), mode
+        assert (rel(bx[..., 0, 1], det[..., 10] - det[..., 6] / 2)[use] <= b[10] + b[6]).all(), mode
+
+
+def settings_cases():
+    """(head set, setting) pairs beyond runs/monoflex.yaml with the full set: every setting of tests/decode_cfg_ref.py (depth_decode exp / linear,
+    linear dimensions, the std switch, custom means, DEPTH_RANGE [1, 60], one and two classes) on the full set, every reduced set of
+    tests/head_sets_ref.py under the yaml settings (soft / hard / mean over the three keypoint depths alone, no sigma heads), and two
+    combinations of both."""
+    from tests import decode_cfg_ref as DC
+    from tests import head_sets_ref as HS
+    return [("s111", st) for st in DC.SETTINGS] + [(n, "yaml") for n in HS.SETS if n != "s111"] + [("s011", "b_linear_depth"), ("s010", "a_linear_std")]
+
+
+@pytest.mark.parametrize("name,setting", settings_cases())
+def test_pred_box_under_other_settings_and_head_sets(shim, name, setting):
+    """Box 0 (and with it decode_dims, decode_estimates and output_depth of eval_diag_math.h) under the non-yaml head settings and the reduced
+    head sets PostProcessor accepts with EVAL_DIS_IOUS: against the float64 decode of tests/head_sets_ref.py for the same pixel and class,
+    at the bounds the decode kernel is held to under that setting (tests/decode_cfg_ref.py)."""
+    from tests import decode_cfg_ref as DC
+    from tests import head_sets_ref as HS
+    st = DC.YAML if setting == "yaml" else DC.SETTINGS[setting]
+    ncls = st["ncls"]
+    S = HS.yaml_settings(**{k: st[k] for k in ("depth_mode", "depth_ref", "depth_range", "dim_exp", "dim_use_std", "dim_mean", "dim_std", "uncertainty_as_conf")})
+    d = dict(E.case_inputs("b4_m70"))
+    off = d["reg_off"]
+    d["hmap"] = HS.take(d["hmap"][..., off:off + 50], name, 3, ld=d["ld"], off=off, junk=d["hmap"])       # the set's R channels at [off, off + R)
+    gt = d["gt_rows"].copy()
+    gt[..., 1] = gt[..., 1].astype(np.int64) % ncls
+    d["gt_rows"] = gt
+    hs = L.HeadSet(HS.SETS[name], HS.channels(name))
+    scores, index = E.census_lists(d, ncls)
+    v = gt[..., 0] != 0
+    b = DC.bounds(setting)
+    col = {c: i for i, c in enumerate(D.COLUMNS)}
+    rel = lambda got, want: np.abs(got - want) / np.maximum(1.0, np.abs(want))
+    lib_settings = dict(depth_mode=st["depth_mode"], depth_range=st["depth_range"], depth_ref=st["depth_ref"], dim_mean=st["dim_mean"][:ncls],
+                        dim_std=st["dim_std"][:ncls], dim_modes=["exp" if st["dim_exp"] else "linear", True, st["dim_use_std"]], down_ratio=4, eps=1e-3)
+    modes = [m for m in D.MODES if m in hs.output_depths()]
+    assert modes
+    for mode in modes:
+        cfg = L.decode_cfg(lib_settings, st["uncertainty_as_conf"], mode)
+        _, iou, bx = shim(d, mode, want=2, cfg=cfg, heads=hs.layout())
+        dr = HS.decode_ref(name, d["hmap"], off, scores, index, d["calib"], d["pad"], np.array([160, 96]), C.THRESHOLD, mode, S)
+        det = dr["det"]
+        assert (det[..., 0][v] == gt[..., 1][v]).all()
+        use = v & ~D.near_rows(dr, mode)
+        assert use.sum() >= 0.98 * v.sum()
+        for mine, theirs in ((0, "X"), (2, "Z"), (3, "l"), (4, "h"), (5, "w")):
+            assert (rel(bx[..., 0, mine], det[..., col[theirs]])[use] <= b[col[theirs]]).all(), (mode, theirs, rel(bx[..., 0, mine], det[..., col[theirs]])[use].max())
+        ry = np.abs(bx[..., 0, 6] - det[..., 12])
+        ry = np.minimum(ry, np.abs(ry - 2 * np.pi)) / np.maximum(1.0, np.abs(det[..., 12]))
+        assert (ry[use] <= b[12]).all(), mode
+        assert (rel(bx[..., 0, 1], det[..., 10] - det[..., 6] / 2)[use] <= b[10] + b[6]).all(), mode
+        # the predicted dimensions and depth are the same values in the boxes that reuse them, and the IoUs are those of these boxes
+        assert np.array_equal(bx[..., 4, 3:6], bx[..., 0, 3:6]) and np.array_equal(bx[..., 3, 2], bx[..., 0, 2])
+        want_iou = R.iou_of_boxes(bx[v])
+        assert (np.abs(iou[v] - want_iou) <= R.IOU_TOL * np.maximum(1.0, np.abs(want_iou))).all(), mode
+
+
+def test_only_the_objects_own_rows_are_read(shim):
+    """NaN everywhere but the regression channels of the valid objects' centre pixels, and NaN in every empty slot's row: same tables."""
+    d = E.case_inputs("b4_m40_ld72")
+    want = shim(d, "soft")
+    hm = np.full_like(d["hmap"], np.nan)
+    gt = d["gt_rows"].copy()
+    valid = gt[..., 0] != 0
+    for b, m in zip(*np.nonzero(valid)):
+        cx, cy = int(gt[b, m, 2]), int(gt[b, m, 3])
+        hm[b, cy, cx, d["reg_off"]:d["reg_off"] + 50] = d["hmap"][b, cy, cx, d["reg_off"]:d["reg_off"] + 50]
+    gt[~valid, 1:] = np.nan
+    gt[..., 13:] = np.nan                                              # the spare columns
+    got = shim(d, "soft", hmap=hm, gt_rows=gt)
+    for a, b_ in zip(want, got):
+        assert np.array_equal(a, b_)
+
+
+def test_out_of_range_rows_read_nothing(shim):
+    d = E.case_inputs("b3_m40")
+    gt = d["gt_rows"].copy()
+    valid = np.nonzero(gt[0, :, 0])[0]
+    gt[0, valid[0], 2] = E.W                                           # centre one past the last column
+    gt[0, valid[1], 3] = -1                                            # above the first row
+    gt[0, valid[2], 1] = 3                                             # a class without a dimension row
+    de, iou, bx = shim(d, "direct", gt_rows=gt)
+    ok = shim(d, "direct")
+    for m in valid[:3]:
+        assert np.isnan(de[0, m]).all() and np.isnan(iou[0, m]).all() and np.isnan(bx[0, m]).all()
+    keep = np.ones(gt.shape[:2], dtype=bool)
+    keep[0, valid[:3]] = False
+    assert np.array_equal(de[keep], ok[0][keep]) and np.array_equal(iou[keep], ok[1][keep])
+
+
+def test_config_refusals_of_the_entry(shim):
+    from tests import head_sets_ref as HS
+    d = E.case_inputs("b1_m1")
+    for want in (0, 4, -1):
+        with pytest.raises(ValueError, match="want must be"):
+            shim(d, "soft", want=want)
+    for name in HS.SETS:
+        du, kp, cu = HS.flags(name)
+        hs = L.HeadSet(HS.SETS[name], HS.channels(name))
+        small = dict(d, hmap=d["hmap"][..., :64])
+        if not (du and kp and cu):
+            with pytest.raises(ValueError, match="depth errors need"):
+                shim(small, "direct", want=1, heads=hs.layout())
+        for mode in D.MODES:
+            if mode in hs.output_depths():
+                shim(small, mode, want=2, heads=hs.layout())
+            else:
+                with pytest.raises(ValueError, match="output_depth"):
+                    shim(small, mode, want=2, heads=hs.layout())
+    bad = E.yaml_cfg("soft")
+    bad.output_depth = 8
+    with pytest.raises(ValueError, match="MFX_DEPTH"):
+        shim(d, "soft", cfg=bad)
+    with pytest.raises(ValueError, match="reach outside a row"):
+        shim(dict(d, reg_off=20), "soft")
+
+
+# ---- ABI ------------------------------------------------------------------------------------------------------------------------------
+def test_abi_declaration_and_constants():
+    header = open(os.path.join(ROOT, "include", "monoflex_hip.h")).read()
+    m = re.search(r"int mfx_eval_diagnostics\((.*?)\);", header, re.S)
+    assert m, "mfx_eval_diagnostics is not declared"
+    params = [p.strip() for p in m.group(1).replace("\n", " ").split(",")]
+    res, args = L.SYMBOLS["mfx_eval_diagnostics"]
+    assert res is ctypes.c_int and len(args) == len(params) == 17
+    for p, a in zip(params, args):
+        if "mfx_decode_cfg" in p:
+            assert a is ctypes.POINTER(L.DecodeCfg)
+        elif "mfx_head_layout" in p:
+            assert a is ctypes.POINTER(L.HeadLayout)
+        else:
+            assert a is (ctypes.c_void_p if "*" in p else ctypes.c_int), p
+    consts = dict(re.findall(r"(MFX_EVAL_\w+) = (\d+)", header))
+    assert int(consts["MFX_EVAL_GT_ROW"]) == ops.EVAL_GT_ROW == R.GT_ROW == 16
+    assert int(consts["MFX_EVAL_DEPTH_KEYS"]) == len(ops.EVAL_DEPTH_KEYS) == 13 and int(consts["MFX_EVAL_IOU_KEYS"]) == len(ops.EVAL_IOU_KEYS) == 5
+    assert ops.EVAL_DEPTH_KEYS == R.DEPTH_KEYS and ops.EVAL_IOU_KEYS == R.IOU_KEYS
+    assert re.search(r"#define MFX_ABI_VERSION 3\b", header)
+    assert "eval_diag.hip" in __import__("monoflex_amd.build", fromlist=["SOURCES"]).SOURCES
+
+
+def test_eval_diag_rows_from_fields_and_targets():
+    from monoflex_amd.structures.params_3d import ParamsList
+    d = E.case_inputs("b3_m40")
+    gt = torch.from_numpy(d["gt_rows"])
+    fields = dict(reg_mask=gt[..., 0].to(torch.uint8), cls_ids=gt[..., 1].long(), target_centers=gt[..., 2:4].long(), offset_3D=gt[..., 4:6],
+                  locations=gt[..., 6:9], dimensions=gt[..., 9:12], rotys=gt[..., 12])
+    want = gt.clone()
+    want[..., 13:] = 0
+    want[..., 1:4] = want[..., 1:4].long().float()                    # class and centre are integer fields (an empty slot of the cases holds noise)
+    rows = ops.eval_diag_rows(fields, "cpu")
+    assert rows.dtype == torch.float32 and torch.equal(rows, want)
+    targets = []
+    for b in range(gt.shape[0]):
+        t = ParamsList((160, 96), is_train=False)
+        for k, v in fields.items():
+            t.add_field(k, v[b])
+        targets.append(t)
+    assert torch.equal(ops.eval_diag_rows(targets, "cpu"), want)
+    with pytest.raises(ValueError, match="no .*rotys"):
+        ops.eval_diag_rows({k: v for k, v in fields.items() if k != "rotys"}, "cpu")
+
+
+# ---- PostProcessor: what is refused, and when -------------------------------------------------------------------------------------------
+def post_for(name, depth, eval_depth, eval_dis):
+    from monoflex_amd.model.head.detector_infer import make_post_processor
+    return make_post_processor(HC.cfg_for(name, extra=["MODEL.HEAD.OUTPUT_DEPTH", depth, "TEST.EVAL_DEPTH", eval_depth, "TEST.EVAL_DIS_IOUS", eval_dis]))
+
+
+def test_refusal_matrix():
+    from tests import head_sets_ref as HS
+    for name in HS.SETS:
+        full = all(HS.flags(name))
+        served = HS.output_depths(name)
+        base = "soft" if "soft" in served else "direct"
+        assert post_for(name, base, False, False).diagnostics_wanted == 0
+        if full:
+            assert post_for(name, base, True, False).diagnostics_wanted == 1
+        else:
+            with pytest.raises(NotImplementedError, match="EVAL_DEPTH"):
+                post_for(name, base, True, False)
+        for mode in D.MODES:
+            if mode in served:
+                assert post_for(name, mode, False, True).diagnostics_wanted == 2
+            else:
+                with pytest.raises(NotImplementedError, match="OUTPUT_DEPTH"):
+                    post_for(name, mode, False, True)
+    with pytest.raises(NotImplementedError, match="oracle"):
+        post_for("s111", "oracle", False, True)
+    p = post_for("s111", "oracle", True, False)                        # the depth errors do not read output_depth
+    assert p.diagnostics_wanted == 1
+    p = post_for("s111", "soft", True, True)
+    assert p.diagnostics_wanted == 3 and p.eval_depth and p.eval_dis_iou
+    # output_depth is read per call: re-assigned to what cannot be served, the call refuses before any launch
+    p.output_depth = "oracle"
+    with pytest.raises(NotImplementedError, match="oracle"):
+        p.diagnose_device(None, None, None, None)
+
+
+def test_test_split_targets_raise():
+    from monoflex_amd import synthetic as S
+    from monoflex_amd.structures.params_3d import make_test_target
+    p = post_for("s111", "soft", True, True)
+    t = make_test_target(S.synthetic_target(E.W, E.H))
+    with pytest.raises(ValueError, match="test. split"):
+        p({"hm_nhwc": torch.zeros(1, E.H, E.W, 64), "cls": None}, [t], test=True)
+    off = post_for("s111", "soft", False, False)
+    assert off.diagnose_device(None, None, None, None) == (None, None)
+
+
+def test_diagnostics_tables_order():
+    from monoflex_amd.model.head.detector_infer import PostProcessor
+    de = torch.arange(2 * 3 * 13, dtype=torch.float32).reshape(2, 3, 13)
+    iou = torch.arange(2 * 3 * 5, dtype=torch.float32).reshape(2, 3, 5)
+    mask = torch.tensor([[0, 1, 1], [1, 0, 1]])
+    a, b = PostProcessor.diagnostics_tables(de, iou, mask)
+    assert tuple(a) == R.DEPTH_KEYS and tuple(b) == R.IOU_KEYS
+    assert a["direct"].tolist() == [13.0, 26.0, 39.0, 65.0] and b["orien_IoU"].tolist() == [9.0, 14.0, 19.0, 29.0]       # (image, slot) order
+    assert PostProcessor.diagnostics_tables(None, iou, mask)[0] is None
+
+
+# ---- inference(): aggregation and log lines on canned tables -------------------------------------------------------------------------------
+class CannedModel(torch.nn.Module):
+    """Stands in for the detector on the sequential path: per batch the eval_utils PostProcessor.forward would return."""
+
+    def __init__(self, batches, want):
+        super().__init__()
+        self.batches, self.calls = batches, 0
+        self.heads = torch.nn.Module()
+        self.heads.post_processor = torch.nn.Module()
+        self.heads.post_processor.diagnostics_wanted = want
+        self.heads.post_processor.output_depth = "soft"
+
+    def forward(self, images, targets):
+        de, iou = self.batches[self.calls]
+        self.calls += 1
+        utils = {"depth_errors": None if de is None else {k: de[:, i] for i, k in enumerate(R.DEPTH_KEYS)},
+                 "dis_ious": None if iou is None else {k: iou[:, i] for i, k in enumerate(R.IOU_KEYS)}}
+        return [torch.zeros(0, 14) for _ in range(images.shape[0])], utils, None
+
+
+class CannedTarget:
+    def to(self, device):
+        return self
+
+
+def canned_loader(n_batches):
+    class DS:
+        label_dir, imageset_txt, classes = "labels", "val.txt", ("Car",)
+    batches = [dict(images=torch.zeros(2, 3, 8, 8), targets=[CannedTarget(), CannedTarget()], img_ids=["%06d" % (2 * i), "%06d" % (2 * i + 1)])
+               for i in range(n_batches)]
+
+    class Loader(list):
+        dataset = DS()
+    return Loader(batches)
+
+
+def test_inference_aggregates_and_logs(tmp_path, monkeypatch, caplog):
+    from monoflex_amd.engine import inference as INF
+    monkeypatch.setattr(INF, "evaluate_python", lambda **kw: ("Car AP", {"Car_3d_0.70/moderate": 1.0}))
+    g = torch.Generator().manual_seed(3)
+    tables = [(torch.rand(4, 13, generator=g), torch.rand(4, 5, generator=g)), (torch.rand(0, 13), torch.rand(0, 5)),
+              (torch.rand(3, 13, generator=g), torch.rand(3, 5, generator=g))]
+    de = torch.cat([t[0] for t in tables]).double().mean(dim=0)
+    iou = torch.cat([t[1] for t in tables]).double().mean(dim=0)
+    diag = {}
+    n = INF.compute_on_dataset(CannedModel(tables, 3), canned_loader(3), "cpu", str(tmp_path), diagnostics=diag)
+    assert n == 6 and diag["objects"] == 7
+    assert tuple(diag["dis_ious"]) == R.IOU_KEYS and tuple(diag["depth_errors"]) == R.DEPTH_KEYS
+    for i, k in enumerate(R.IOU_KEYS):
+        assert abs(diag["dis_ious"][k] - float(iou[i])) <= 1e-12
+    for i, k in enumerate(R.DEPTH_KEYS):
+        assert abs(diag["depth_errors"][k] - float(de[i])) <= 1e-12
+    # inference(): the reference's line per IoU key, one line per depth key, the IoU means as the third value
+    with caplog.at_level(logging.INFO, logger="monoflex.inference"):
+        _, _, third = INF.inference(CannedModel(tables, 3), canned_loader(3), "val", device="cpu", output_folder=str(tmp_path / "o"))
+    assert third == diag["dis_ious"]
+    text = caplog.text
+    for k in R.IOU_KEYS:
+        assert "%s, MEAN IOU = %.4f" % (k, diag["dis_ious"][k]) in text
+    for k in R.DEPTH_KEYS:
+        assert "depth %s, MEAN = %.4f" % (k, diag["depth_errors"][k]) in text
+    # one flag only; no object at all: nan; both flags off: {} and no line
+    diag = {}
+    INF.compute_on_dataset(CannedModel([(t[0], None) for t in tables], 1), canned_loader(3), "cpu", str(tmp_path), diagnostics=diag)
+    assert diag["dis_ious"] == {} and tuple(diag["depth_errors"]) == R.DEPTH_KEYS and diag["objects"] == 7
+    diag = {}
+    INF.compute_on_dataset(CannedModel([tables[1]], 3), canned_loader(1), "cpu", str(tmp_path), diagnostics=diag)
+    assert diag["objects"] == 0 and all(np.isnan(v) for v in diag["dis_ious"].values()) and len(diag["depth_errors"]) == 13
+    caplog.clear()
+    with caplog.at_level(logging.INFO, logger="monoflex.inference"):
+        _, _, third = INF.inference(CannedModel([(None, None)] * 3, 0), canned_loader(3), "val", device="cpu", output_folder=str(tmp_path / "p"))
+    assert third == {} and "MEAN IOU" not in caplog.text and "MEAN =" not in caplog.text
