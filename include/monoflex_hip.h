@@ -638,7 +638,7 @@ int mfx_box3d_iou_pairs(const float* boxes_a, const float* boxes_b, int N, int f
  *   boxes    : optional fp32 [B][M][6][7] rows (x, y, z, l, h, w, ry): 0 predicted (depth by cfg->output_depth, as mfx_decode_boxes_heads
  *              decodes that pixel under that class, Y without the half height), 1 target, 2 predicted offset, 3 predicted depth, 4 predicted
  *              dimensions, 5 predicted orientation -- the rest of 2..5 is ground truth.  The reference builds these under 'direct' only; the
- *              other MFX_DEPTH_* modes follow mfx_decode_boxes_heads' combination and head-set rule.
+ *              other MFX_DEPTH_* modes run the function mfx_decode_boxes_heads runs (csrc/box_decode_math.h bdec::combine).
  * One launch of ceil(B*M/64) 64-lane workgroups on `stream`, nothing allocated, no synchronisation; B*M == 0 returns MFX_OK without a launch. */
 enum { MFX_EVAL_GT_ROW = 16, MFX_EVAL_DEPTH_KEYS = 13, MFX_EVAL_IOU_KEYS = 5, MFX_EVAL_BOXES = 6 };
 int mfx_eval_diagnostics(const float* hmap, int ld, int reg_off, const float* gt_rows, int B, int M, int H, int W,

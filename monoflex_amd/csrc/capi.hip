@@ -11,6 +11,10 @@ int mfx_fail(int code, const char* msg) {
     std::snprintf(g_err, sizeof(g_err), "%s", msg);
     return code;
 }
+int mfx_fail_in(int code, const char* entry, const char* msg) {
+    std::snprintf(g_err, sizeof(g_err), "%s: %s", entry, msg);
+    return code;
+}
 int mfx_fail_hip(hipError_t e, const char* what) {
     std::snprintf(g_err, sizeof(g_err), "HIP error %d (%s) in %s", (int)e, hipGetErrorString(e), what);
     return MFX_ERR_LAUNCH;

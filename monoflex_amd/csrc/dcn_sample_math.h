@@ -36,13 +36,7 @@
 #pragma once
 #include <cmath>
 
-#ifndef MFX_HD
-#ifdef __HIPCC__
-#define MFX_HD __host__ __device__ inline
-#else
-#define MFX_HD inline
-#endif
-#endif
+#include "hd.h"
 
 namespace mfx {
 namespace dcns {

@@ -4,13 +4,13 @@
 // Latency-bound (reads 3*H*W + K*50 values per image); two launches, no host sync.
 #include "../../include/monoflex_hip.h"
 #include "common.h"
+#include "box_decode_math.h"
 #include "err.h"
 #include <cmath>
 
 namespace mfx {
 
 constexpr int kTopkThreads = 1024;
-constexpr float kPi = 3.14159265358979323846f;
 
 __device__ __forceinline__ float sigmoid_clamp(float x) {          // layers/utils.py:39-43
     const float s = 1.f / (1.f + expf(-x));
@@ -277,11 +277,6 @@ __global__ __launch_bounds__(512) void decode_topk_merge_kernel(const float* can
     }
 }
 
-// key2channel offsets of runs/monoflex.yaml:27-28: the layout mfx_decode_boxes_cfg decodes (mfx_decode_boxes_heads takes any)
-enum { R_2D = 0, R_OFF3D = 4, R_KPT = 6, R_KPT_UNC = 26, R_DIM3D = 29, R_ORI_CLS = 32, R_ORI_OFF = 40, R_DEPTH = 48, R_DEPTH_UNC = 49, R_TOTAL = 50 };
-// mfx_head_layout.ch[] order (= mfx_object_loss_cfg.ch[])
-enum { HK_2D = 0, HK_OFF3D, HK_KPT, HK_KPT_UNC, HK_DIM3D, HK_ORI_CLS, HK_ORI_OFF, HK_DEPTH, HK_DEPTH_UNC };
-
 __global__ __launch_bounds__(256) void decode_boxes_kernel(const float* hmap, int ld, int reg_off, const float* scores, const int* index,
                                                            int ncls, int H, int W, int K, const float* calib, const int* pad,
                                                            const int* img_size, float threshold, mfx_decode_cfg dc, mfx_head_layout hl,
@@ -308,135 +303,20 @@ __global__ __launch_bounds__(256) void decode_boxes_kernel(const float* hmap, in
     const int idx = ci[pos];
     const int ys = idx / W, xs = idx - ys * W;                // utils.py:80-81
     const float* r = hmap + ((size_t)b * H * W + idx) * ld + reg_off;   // POI gather: one contiguous NHWC row
-    const float fu = calib[b * 6 + 0], fv = calib[b * 6 + 1], cu = calib[b * 6 + 2], cv = calib[b * 6 + 3];
-    const float bx = calib[b * 6 + 4], by = calib[b * 6 + 5];
-    const float padx = (float)pad[b * 2], pady = (float)pad[b * 2 + 1];
+    const bdec::Camera cam = {calib[b * 6 + 0], calib[b * 6 + 1], calib[b * 6 + 2], calib[b * 6 + 3], calib[b * 6 + 4], calib[b * 6 + 5],
+                              (float)pad[b * 2], (float)pad[b * 2 + 1]};
     const float px = (float)xs, py = (float)ys;
-    // the head set: channel starts of the nine keys in the row; an absent optional key (-1) is never read and its estimate takes no part
-    const int R_2D = hl.ch[HK_2D], R_OFF3D = hl.ch[HK_OFF3D], R_KPT = hl.ch[HK_KPT], R_KPT_UNC = hl.ch[HK_KPT_UNC], R_DIM3D = hl.ch[HK_DIM3D],
-              R_ORI_CLS = hl.ch[HK_ORI_CLS], R_ORI_OFF = hl.ch[HK_ORI_OFF], R_DEPTH = hl.ch[HK_DEPTH], R_DEPTH_UNC = hl.ch[HK_DEPTH_UNC];
-    const bool has_du = R_DEPTH_UNC >= 0, has_kp = R_KPT >= 0, has_cu = has_kp && R_KPT_UNC >= 0;
-
-    // decode_box2d_fcos (anno_encoder.py:69-86); clamp uses image 0's padded size
-    float x1 = (px - fmaxf(r[R_2D + 0], 0.f)) * dc.down_ratio - padx;
-    float y1 = (py - fmaxf(r[R_2D + 1], 0.f)) * dc.down_ratio - pady;
-    float x2 = (px + fmaxf(r[R_2D + 2], 0.f)) * dc.down_ratio - padx;
-    float y2 = (py + fmaxf(r[R_2D + 3], 0.f)) * dc.down_ratio - pady;
-    const float wmax = (float)(img_size[0] - 1), hmax = (float)(img_size[1] - 1);
-    x1 = fminf(fmaxf(x1, 0.f), wmax); x2 = fminf(fmaxf(x2, 0.f), wmax);
-    y1 = fminf(fmaxf(y1, 0.f), hmax); y2 = fminf(fmaxf(y2, 0.f), hmax);
-
-    // decode_dimension (anno_encoder.py:221-243), order (l,h,w): exp(offset) or the offset, then * std[cls] + mean[cls] or * mean[cls]
-    auto dim = [&](int i) {
-        const float off = dc.dim_exp ? expf(r[R_DIM3D + i]) : r[R_DIM3D + i];
-        return dc.dim_use_std ? off * dc.dim_std[cls * 3 + i] + dc.dim_mean[cls * 3 + i] : off * dc.dim_mean[cls * 3 + i];
-    };
-    const float dl = dim(0), dh = dim(1), dw = dim(2);
-
-    // decode_depth (anno_encoder.py:124-140): exp / linear around DEPTH_REFERENCE / inv_sigmoid, then the DEPTH_RANGE clamp
-    const float depth_min = dc.depth_range[0], depth_max = dc.depth_range[1];
-    float d0;
-    if (dc.depth_decode == 0) d0 = expf(r[R_DEPTH]);
-    else if (dc.depth_decode == 1) d0 = r[R_DEPTH] * dc.depth_ref[1] + dc.depth_ref[0];
-    else d0 = 1.f / (1.f / (1.f + expf(-r[R_DEPTH]))) - 1.f;
-    d0 = fminf(fmaxf(d0, depth_min), depth_max);
-    const float u0 = has_du ? expf(r[R_DEPTH_UNC]) : 1.f;
-
-    // decode_depth_from_keypoints_batch (anno_encoder.py:187-219); keypoint k = (r[6+2k], r[7+2k])
-    auto ky = [&](int k) { return has_kp ? r[R_KPT + 2 * k + 1] : 0.f; };
-    auto kdepth = [&](float dy) { return fu * dh / (fmaxf(dy, 0.f) * dc.down_ratio + dc.eps); };
-    float d1 = kdepth(ky(8) - ky(9));
-    float d2 = (kdepth(ky(0) - ky(4)) + kdepth(ky(2) - ky(6))) / 2.f;
-    float d3 = (kdepth(ky(1) - ky(5)) + kdepth(ky(3) - ky(7))) / 2.f;
-    d1 = fminf(fmaxf(d1, depth_min), depth_max);
-    d2 = fminf(fmaxf(d2, depth_min), depth_max);
-    d3 = fminf(fmaxf(d3, depth_min), depth_max);
-    const float u1 = has_cu ? expf(r[R_KPT_UNC + 0]) : 1.f, u2 = has_cu ? expf(r[R_KPT_UNC + 1]) : 1.f, u3 = has_cu ? expf(r[R_KPT_UNC + 2]) : 1.f;
-
-    // which depth leaves the four estimates, and the uncertainty that scales the score with it (detector_infer.py:149-198 `output_depth`)
-    // Without depth_uncertainty soft / hard / mean combine the three keypoint depths alone (:177-182).  has_err: whether the reference has an
-    // estimated_depth_error for this mode at all -- the chosen estimate's own uncertainty head must exist (:148-170); without one the score
-    // stays raw and nothing is reported.
-    float depth, sigma;
-    bool has_err = true;
-    if (dc.output_depth <= MFX_DEPTH_MEAN && !has_du) {
-        if (dc.output_depth == MFX_DEPTH_SOFT) {
-            float w1 = 1.f / u1, w2 = 1.f / u2, w3 = 1.f / u3;
-            const float ws = (w1 + w2) + w3;
-            w1 /= ws; w2 /= ws; w3 /= ws;
-            depth = (d1 * w1 + d2 * w2) + d3 * w3;
-            sigma = (w1 * u1 + w2 * u2) + w3 * u3;
-        } else if (dc.output_depth == MFX_DEPTH_HARD) {
-            const float w1 = 1.f / u1, w2 = 1.f / u2, w3 = 1.f / u3;
-            depth = d1; float wb = w1;
-            if (w2 > wb) { wb = w2; depth = d2; }
-            if (w3 > wb) { wb = w3; depth = d3; }
-            sigma = fminf(u1, fminf(u2, u3));
-        } else {
-            depth = ((d1 + d2) + d3) / 3.f; sigma = ((u1 + u2) + u3) / 3.f;
-        }
-    } else if (dc.output_depth == MFX_DEPTH_SOFT) {             // 'soft' (:186-192; runs/monoflex.yaml)
-        float w0 = 1.f / u0, w1 = 1.f / u1, w2 = 1.f / u2, w3 = 1.f / u3;
-        const float ws = ((w0 + w1) + w2) + w3;
-        w0 /= ws; w1 /= ws; w2 /= ws; w3 /= ws;
-        depth = ((d0 * w0 + d1 * w1) + d2 * w2) + d3 * w3;
-        sigma = ((w0 * u0 + w1 * u1) + w2 * u2) + w3 * u3;
-    } else if (dc.output_depth == MFX_DEPTH_HARD) {             // 'hard' (:180-184): the estimate of the largest weight 1 / u (first of equals, as argmax)
-        const float w0 = 1.f / u0, w1 = 1.f / u1, w2 = 1.f / u2, w3 = 1.f / u3;
-        depth = d0; float wb = w0;
-        if (w1 > wb) { wb = w1; depth = d1; }
-        if (w2 > wb) { wb = w2; depth = d2; }
-        if (w3 > wb) { wb = w3; depth = d3; }
-        sigma = fminf(fminf(u0, u1), fminf(u2, u3));
-    } else if (dc.output_depth == MFX_DEPTH_MEAN) {             // 'mean' (:194-198)
-        depth = (((d0 + d1) + d2) + d3) / 4.f; sigma = (((u0 + u1) + u2) + u3) / 4.f;
-    } else if (dc.output_depth == MFX_DEPTH_DIRECT) {           // 'direct' (:149-152)
-        depth = d0; sigma = u0; has_err = has_du;
-    } else if (dc.output_depth == MFX_DEPTH_KEYPOINTS_AVG) {    // 'keypoints_avg' (:155-157)
-        depth = ((d1 + d2) + d3) / 3.f; sigma = ((u1 + u2) + u3) / 3.f; has_err = has_cu;
-    } else if (dc.output_depth == MFX_DEPTH_KEYPOINTS_CENTER) { depth = d1; sigma = u1; has_err = has_cu; }   // (:159-161)
-    else if (dc.output_depth == MFX_DEPTH_KEYPOINTS_02) { depth = d2; sigma = u2; has_err = has_cu; }          // (:163-165)
-    else { depth = d3; sigma = u3; has_err = has_cu; }                                                         // 'keypoints_13' (:167-169)
-
-    // decode_location_flatten (anno_encoder.py:142-155) + project_image_to_rect (kitti_utils.py:350-369)
-    const float u = (px + r[R_OFF3D + 0]) * dc.down_ratio - padx;
-    const float v = (py + r[R_OFF3D + 1]) * dc.down_ratio - pady;
-    const float X = ((u - cu) * depth) / fu + bx;
-    float Y = ((v - cv) * depth) / fv + by;
-    const float Z = depth;
-
-    // decode_axes_orientation, multi-bin (anno_encoder.py:245-295)
-    int best = 0; float bestp = -1.f;
-    for (int i = 0; i < 4; ++i) {
-        const float a = r[R_ORI_CLS + 2 * i], c = r[R_ORI_CLS + 2 * i + 1];
-        const float m = fmaxf(a, c), e0 = expf(a - m), e1 = expf(c - m);
-        const float p1 = e1 / (e0 + e1);
-        if (p1 > bestp) { bestp = p1; best = i; }
-    }
-    const float centers[4] = {0.f, kPi / 2.f, kPi, -kPi / 2.f};
-    float alpha = atan2f(r[R_ORI_OFF + 2 * best], r[R_ORI_OFF + 2 * best + 1]) + centers[best];
-    float ry = alpha + atan2f(X, Z);
-    if (ry > kPi) ry -= 2.f * kPi;
-    if (ry < -kPi) ry += 2.f * kPi;
-    if (alpha > kPi) alpha -= 2.f * kPi;
-    if (alpha < -kPi) alpha += 2.f * kPi;
-
-    Y += dh / 2.f;                                            // detector_infer.py:215
-    // the depth's uncertainty scales the score under TEST.UNCERTAINTY_AS_CONFIDENCE (:223-229); otherwise the raw score, and no uncertainty is reported
-    const float conf = 1.f - fminf(fmaxf(sigma, 0.01f), 1.f);
-    const bool as_conf = dc.uncertainty_as_conf && has_err;
-    const float final_score = as_conf ? score * conf : score;
+    // the 2D box clamp uses image 0's padded size
+    const bdec::Row row = bdec::decode_row(r, px, py, cls, score, cam, (float)(img_size[0] - 1), (float)(img_size[1] - 1), dc, hl);
 
     float* o = det + ((size_t)b * K + j) * 14;
-    o[0] = (float)cls; o[1] = alpha; o[2] = x1; o[3] = y1; o[4] = x2; o[5] = y2;
-    o[6] = dh; o[7] = dw; o[8] = dl;                          // roll(-1): (l,h,w) -> (h,w,l)
-    o[9] = X; o[10] = Y; o[11] = Z; o[12] = ry; o[13] = final_score;
+    for (int i = 0; i < 14; ++i) o[i] = row.det[i];
     float* t = topk + ((size_t)b * K + j) * 5;
     t[0] = score; t[1] = (float)idx; t[2] = (float)cls; t[3] = py; t[4] = px;
     valid[b * K + j] = score >= threshold ? 1 : 0;
     if (unc) {                                                // [estimated_depth_error, uncertainty_conf]
-        unc[((size_t)b * K + j) * 2 + 0] = as_conf ? sigma : 0.f;
-        unc[((size_t)b * K + j) * 2 + 1] = as_conf ? conf : 0.f;
+        unc[((size_t)b * K + j) * 2 + 0] = row.as_conf ? row.sigma : 0.f;
+        unc[((size_t)b * K + j) * 2 + 1] = row.as_conf ? row.conf : 0.f;
     }
 }
 
@@ -507,6 +387,7 @@ extern "C" int mfx_decode_boxes_cfg(const float* hmap, int ld, int reg_off, cons
                                     int ncls, int B, int H, int W, int K, const float* calib, const int32_t* pad,
                                     const int32_t* img_size, float threshold, const mfx_decode_cfg* cfg, float* det, float* topk, int32_t* valid,
                                     float* unc, void* stream) {
+    using namespace bdec;
     const mfx_head_layout full = {{R_2D, R_OFF3D, R_KPT, R_KPT_UNC, R_DIM3D, R_ORI_CLS, R_ORI_OFF, R_DEPTH, R_DEPTH_UNC}, R_TOTAL};
     return mfx_decode_boxes_heads(hmap, ld, reg_off, scores, index, ncls, B, H, W, K, calib, pad, img_size, threshold, cfg, &full, det, topk, valid, unc, stream);
 }
@@ -519,31 +400,15 @@ extern "C" int mfx_decode_boxes_heads(const float* hmap, int ld, int reg_off, co
     if (!heads) return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: null heads");
     if (!hmap || !scores || !index || !calib || !pad || !img_size || !det || !topk || !valid)
         return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: null pointer");
-    if (cfg->depth_decode < 0 || cfg->depth_decode > 2) return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: depth_decode must be 0 (exp), 1 (linear) or 2 (inv_sigmoid)");
-    if (cfg->output_depth < MFX_DEPTH_SOFT || cfg->output_depth > MFX_DEPTH_KEYPOINTS_13)
-        return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: output_depth must be one of MFX_DEPTH_*");
-    if (!std::isfinite(cfg->depth_range[0]) || !std::isfinite(cfg->depth_range[1]) || cfg->depth_range[0] > cfg->depth_range[1])
-        return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: depth_range must be finite with depth_range[0] <= depth_range[1]");
+    if (const char* e = bdec::decode_cfg_error(*cfg)) return mfx_fail_in(MFX_ERR_ARG, "decode_boxes_heads", e);
     if (ncls < 1 || ncls > 3) return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: need 1 <= ncls <= 3 (rows of dim_mean / dim_std)");
     if (K < 1 || K > 256) return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: need 1 <= K <= 256");
+    const char* e = bdec::head_layout_error(heads->ch, heads->reg_width);
+    if (!e) e = bdec::output_depth_error(cfg->output_depth, *heads);
+    if (e) return mfx_fail_in(MFX_ERR_ARG, "decode_boxes_heads", e);
     const int R = heads->reg_width;
-    if (R < 1 || R > R_TOTAL) return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: reg_width must be 1..50");
     if (B < 0 || H < 1 || W < 1 || ld < R || reg_off < 0 || reg_off + R > ld)
         return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: need B >= 0, H, W >= 1 and the regression channels inside a row (reg_off + reg_width <= ld)");
-    {
-        const int width[9] = {4, 2, 20, 3, 3, 8, 8, 1, 1};
-        for (int i = 0; i < 9; ++i) {
-            const bool optional = i == HK_KPT || i == HK_KPT_UNC || i == HK_DEPTH_UNC;
-            if (heads->ch[i] < 0 && !(optional && heads->ch[i] == -1)) return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: a required regression key is absent");
-            if (heads->ch[i] >= 0 && heads->ch[i] + width[i] > R) return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: a regression key's channels reach past reg_width");
-        }
-        const bool kp = heads->ch[HK_KPT] >= 0, cu = heads->ch[HK_KPT_UNC] >= 0;
-        if (cu && !kp) return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: corner_uncertainty without corner_offset");
-        // detector_infer.py:148-204: keypoints_* read the keypoint depths; soft / hard / mean read them and their uncertainties
-        if (cfg->output_depth >= MFX_DEPTH_KEYPOINTS_AVG && !kp) return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: output_depth keypoints_* needs corner_offset");
-        if (cfg->output_depth <= MFX_DEPTH_MEAN && !(kp && cu))
-            return mfx_fail(MFX_ERR_ARG, "decode_boxes_heads: output_depth soft / hard / mean needs corner_offset and corner_uncertainty");
-    }
     if (B == 0) return MFX_OK;
     const size_t smem = (size_t)ncls * K * 8 + (size_t)K * 4;
     hipLaunchKernelGGL(decode_boxes_kernel, dim3(B), dim3(256), smem, reinterpret_cast<hipStream_t>(stream),

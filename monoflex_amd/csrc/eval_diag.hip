@@ -32,7 +32,7 @@ extern "C" int mfx_eval_diagnostics(const float* hmap, int ld, int reg_off, cons
                                     int want, float* depth_err, float* iou, float* boxes, void* stream) {
     if (!cfg) return mfx_fail(MFX_ERR_ARG, "eval_diagnostics: null cfg");
     if (!heads) return mfx_fail(MFX_ERR_ARG, "eval_diagnostics: null heads");
-    if (const char* e = mfx::ediag::config_error(*cfg, *heads, want)) return mfx_fail(MFX_ERR_ARG, e);
+    if (const char* e = mfx::ediag::config_error(*cfg, *heads, want)) return mfx_fail_in(MFX_ERR_ARG, "eval_diagnostics", e);
     if (B < 0 || M < 0 || H < 1 || W < 1 || (long)B * M > 0x7fffffffL / 64 || reg_off < 0 || ld < heads->reg_width || reg_off + heads->reg_width > ld)
         return mfx_fail(MFX_ERR_ARG, "eval_diagnostics: need B, M >= 0, H, W >= 1 and the regression channels inside a row (reg_off + reg_width <= ld)");
     if (boxes && !(want & 2)) return mfx_fail(MFX_ERR_ARG, "eval_diagnostics: boxes given without want bit 1");

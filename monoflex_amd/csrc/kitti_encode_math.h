@@ -15,11 +15,7 @@
 
 #include "../../include/monoflex_hip.h"
 
-#ifdef __HIPCC__
-#define MFX_HD __host__ __device__ inline
-#else
-#define MFX_HD inline
-#endif
+#include "hd.h"
 
 namespace mfx {
 namespace kitti {

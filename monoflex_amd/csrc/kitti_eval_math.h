@@ -10,13 +10,7 @@
 
 #include "../../include/monoflex_hip.h"
 
-#ifndef MFX_HD
-#ifdef __HIPCC__
-#define MFX_HD __host__ __device__ inline
-#else
-#define MFX_HD inline
-#endif
-#endif
+#include "hd.h"
 
 namespace mfx {
 namespace keval {

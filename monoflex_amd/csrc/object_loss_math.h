@@ -18,14 +18,7 @@
 
 #include "../../include/monoflex_hip.h"
 #include "box3d_iou_math.h"
-
-#ifndef MFX_HD
-#ifdef __HIPCC__
-#define MFX_HD __host__ __device__ inline
-#else
-#define MFX_HD inline
-#endif
-#endif
+#include "box_decode_math.h"
 
 namespace mfx {
 namespace oloss {
@@ -40,7 +33,9 @@ enum { T_BBOX = 0, T_DEPTH, T_OFFSET, T_TRUNC_OFFSET, T_ORIEN, T_DIMS, T_CORNER,
        V_MEAN_MAE, V_IOU3D };
 static_assert(V_IOU3D == 21 && V_IOU3D < NVAL, "the logged 3D IoU is value slot 21");
 enum { N_V = 0, N_V2D, N_V_INSIDE, N_TRUNC, N_KMASK, N_KD_VALID, N_KD_INVALID, N_ORI };
-enum { C_2D = 0, C_OFF3D, C_CORNER, C_CORNER_UNC, C_DIM, C_ORI_CLS, C_ORI_OFF, C_DEPTH, C_DEPTH_UNC };
+// cfg.ch[] is in bdec's key order
+using bdec::HK_2D; using bdec::HK_OFF3D; using bdec::HK_KPT; using bdec::HK_KPT_UNC; using bdec::HK_DIM3D; using bdec::HK_ORI_CLS;
+using bdec::HK_ORI_OFF; using bdec::HK_DEPTH; using bdec::HK_DEPTH_UNC;
 constexpr int MAX_REG = 50;                                        // the full head set's width; a reduced set is 26..49 wide
 
 // regression width the caller states (cfg.reg_width; 0 = the full 50)
@@ -48,18 +43,10 @@ MFX_HD int reg_width(const mfx_object_loss_cfg& c) { return c.reg_width == 0 ? M
 // What is wrong with a head set / corner depth mode, or nullptr: the required keys present and inside the row, corner_uncertainty only
 // next to corner_offset, keypoint_mean only with keypoints, soft / hard combine only with all four depth estimates and their uncertainties.
 inline const char* head_set_error(const mfx_object_loss_cfg& c) {
-    const int R = reg_width(c);
-    const int width[9] = {4, 2, 20, 3, 3, 8, 8, 1, 1};
-    if (R < 1 || R > MAX_REG) return "reg_width outside 1..50";
-    for (int i = 0; i < 9; ++i) {
-        const bool optional = i == C_CORNER || i == C_CORNER_UNC || i == C_DEPTH_UNC;
-        if (c.ch[i] < 0 && !(optional && c.ch[i] == -1)) return "a required regression key is absent (channel start < 0)";
-        if (c.ch[i] >= 0 && c.ch[i] + width[i] > R) return "a regression key's channels reach past the row (channel start + width > reg_width)";
-    }
-    if (c.ch[C_CORNER_UNC] >= 0 && c.ch[C_CORNER] < 0) return "corner_uncertainty without corner_offset";
+    if (const char* e = bdec::head_layout_error(c.ch, reg_width(c))) return e;
     if (c.corner_depth_mode < 0 || c.corner_depth_mode > 3) return "corner_depth_mode outside 0..3";
-    if (c.corner_depth_mode == 1 && c.ch[C_CORNER] < 0) return "corner_depth_mode keypoint_mean needs corner_offset";
-    if (c.corner_depth_mode >= 2 && (c.ch[C_CORNER] < 0 || c.ch[C_CORNER_UNC] < 0 || c.ch[C_DEPTH_UNC] < 0))
+    if (c.corner_depth_mode == 1 && c.ch[HK_KPT] < 0) return "corner_depth_mode keypoint_mean needs corner_offset";
+    if (c.corner_depth_mode >= 2 && (c.ch[HK_KPT] < 0 || c.ch[HK_KPT_UNC] < 0 || c.ch[HK_DEPTH_UNC] < 0))
         return "corner_depth_mode soft_combine / hard_combine needs corner_offset, corner_uncertainty and depth_uncertainty";
     return nullptr;
 }
@@ -132,11 +119,11 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
     const float* pad = t + R_PAD;
     const float t_depth = t[R_DEPTH];
     const float inv_v = 1.f / cnt(N_V);
-    const bool has_du = c.ch[C_DEPTH_UNC] >= 0, has_kp = c.ch[C_CORNER] >= 0, has_cu = has_kp && c.ch[C_CORNER_UNC] >= 0;
+    const bool has_du = c.ch[HK_DEPTH_UNC] >= 0, has_kp = c.ch[HK_KPT] >= 0, has_cu = has_kp && c.ch[HK_KPT_UNC] >= 0;
 
     // ---- 2D box: GIoU / IoU of the four ReLU'ed side distances (iou_loss.py:12-49) ---------------------------------------------
     if (box[3] - box[1] > 0.f && box[2] - box[0] > 0.f) {
-        const Dual pl = drelu(X(c.ch[C_2D])), pt = drelu(X(c.ch[C_2D] + 1)), pr = drelu(X(c.ch[C_2D] + 2)), pb = drelu(X(c.ch[C_2D] + 3));
+        const Dual pl = drelu(X(c.ch[HK_2D])), pt = drelu(X(c.ch[HK_2D] + 1)), pr = drelu(X(c.ch[HK_2D] + 2)), pb = drelu(X(c.ch[HK_2D] + 3));
         const Dual tl = K(px - box[0]), tt = K(py - box[1]), tr = K(box[2] - px), tb = K(box[3] - py);
         const Dual t_area = (tl + tr) * (tt + tb), p_area = (pl + pr) * (pt + pb);
         const Dual w_i = dmin(pl, tl) + dmin(pr, tr), h_i = dmin(pb, tb) + dmin(pt, tt);
@@ -149,18 +136,18 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
     }
 
     // ---- decoded predictions ---------------------------------------------------------------------------------------------------
-    const Dual p_depth = decode_depth(X(c.ch[C_DEPTH]), c);
-    const Dual d_unc = has_du ? dclamp(X(c.ch[C_DEPTH_UNC]), c.unc_lo, c.unc_hi) : K(0.f);
+    const Dual p_depth = decode_depth(X(c.ch[HK_DEPTH]), c);
+    const Dual d_unc = has_du ? dclamp(X(c.ch[HK_DEPTH_UNC]), c.unc_lo, c.unc_hi) : K(0.f);
     Dual p_dims[3];
     for (int k = 0; k < 3; ++k) {                                   // anno_encoder.py:217-239
-        Dual o = X(c.ch[C_DIM] + k);
+        Dual o = X(c.ch[HK_DIM3D] + k);
         if (c.dim_exp) o = dexp(o);
         p_dims[k] = c.dim_use_std ? o * c.dim_std[cls * 3 + k] + c.dim_mean[cls * 3 + k] : o * c.dim_mean[cls * 3 + k];
     }
     Dual kx[10], ky[10];
     for (int j = 0; j < 10; ++j) {
-        kx[j] = has_kp ? X(c.ch[C_CORNER] + 2 * j) : K(0.f);
-        ky[j] = has_kp ? X(c.ch[C_CORNER] + 2 * j + 1) : K(0.f);
+        kx[j] = has_kp ? X(c.ch[HK_KPT] + 2 * j) : K(0.f);
+        ky[j] = has_kp ? X(c.ch[HK_KPT] + 2 * j + 1) : K(0.f);
     }
     // depths from the three keypoint groups (anno_encoder.py:185-215); the focal length is the reference's rank-indexed one
     Dual kd[3] = {K(0.f), K(0.f), K(0.f)};
@@ -173,7 +160,7 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
         for (int g = 0; g < 3; ++g) kd[g] = dclamp(kd[g], c.depth_range[0], c.depth_range[1]);
     }
     Dual c_unc[3];
-    for (int g = 0; g < 3; ++g) c_unc[g] = has_cu ? dclamp(X(c.ch[C_CORNER_UNC] + g), c.unc_lo, c.unc_hi) : K(0.f);
+    for (int g = 0; g < 3; ++g) c_unc[g] = has_cu ? dclamp(X(c.ch[HK_KPT_UNC] + g), c.unc_lo, c.unc_hi) : K(0.f);
     // uncertainty-weighted combination of the depth estimates: all four, or (no depth_uncertainty) the three keypoint depths alone
     // (detector_loss.py:396-403); without corner_uncertainty there is no combination and `soft` stays 0
     const Dual comb_depth[4] = {p_depth, kd[0], kd[1], kd[2]};
@@ -190,19 +177,19 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
     if (c.corner_depth_mode == 1) corner_depth = (kd[0] + kd[1] + kd[2]) / 3.f;
     else if (c.corner_depth_mode == 2) corner_depth = soft;
     else if (c.corner_depth_mode == 3) corner_depth = comb_depth[amin];
-    const Dual ox = X(c.ch[C_OFF3D]), oy = X(c.ch[C_OFF3D] + 1);
+    const Dual ox = X(c.ch[HK_OFF3D]), oy = X(c.ch[HK_OFF3D] + 1);
     const Vec3 p_loc = decode_location(px, py, ox, oy, corner_depth, cal, pad, c.down_ratio);
     // multi-bin yaw (anno_encoder.py:241-295): the most confident bin's residual + its centre, + the viewing-ray angle
     Dual p_roty;
     {
         int best = 0; float bconf = -1.f;
         for (int i = 0; i < 4; ++i) {
-            const float a = X(c.ch[C_ORI_CLS] + 2 * i).v, b = X(c.ch[C_ORI_CLS] + 2 * i + 1).v;
+            const float a = X(c.ch[HK_ORI_CLS] + 2 * i).v, b = X(c.ch[HK_ORI_CLS] + 2 * i + 1).v;
             const float m = fmaxf(a, b), conf = expf(b - m) / (expf(a - m) + expf(b - m));
             if (conf > bconf) { bconf = conf; best = i; }
         }
         const float centers[4] = {0.f, PI / 2, PI, -PI / 2};
-        const Dual alpha = datan2(X(c.ch[C_ORI_OFF] + 2 * best), X(c.ch[C_ORI_OFF] + 2 * best + 1)) + centers[best];
+        const Dual alpha = datan2(X(c.ch[HK_ORI_OFF] + 2 * best), X(c.ch[HK_ORI_OFF] + 2 * best + 1)) + centers[best];
         p_roty = alpha + datan2(p_loc.x, p_loc.z);
         if (p_roty.v > PI) p_roty = p_roty - 2 * PI;
         if (p_roty.v < -PI) p_roty = p_roty + 2 * PI;
@@ -229,13 +216,13 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
     {
         Dual ce = K(0.f), rg = K(0.f);
         for (int i = 0; i < 4; ++i) {
-            const Dual a = X(c.ch[C_ORI_CLS] + 2 * i), b = X(c.ch[C_ORI_CLS] + 2 * i + 1);
+            const Dual a = X(c.ch[HK_ORI_CLS] + 2 * i), b = X(c.ch[HK_ORI_CLS] + 2 * i + 1);
             const float m = fmaxf(a.v, b.v);
             const Dual lse = dlog(dexp(a - m) + dexp(b - m)) + m;
             const bool is_bin = t[R_ORI + i] == 1.f;
             ce = ce + (lse - ((int)t[R_ORI + i] == 1 ? b : a));
             if (is_bin) {
-                const Dual s = X(c.ch[C_ORI_OFF] + 2 * i), q = X(c.ch[C_ORI_OFF] + 2 * i + 1);
+                const Dual s = X(c.ch[HK_ORI_OFF] + 2 * i), q = X(c.ch[HK_ORI_OFF] + 2 * i + 1);
                 const Dual nr = dsqrt(s * s + q * q);
                 const Dual dn = nr.v > 1e-12f ? nr : K(1e-12f);        // F.normalize: x / max(||x||, 1e-12)
                 rg = rg + dabs(s / dn - sinf(t[R_ORI + 4 + i])) + dabs(q / dn - cosf(t[R_ORI + 4 + i]));

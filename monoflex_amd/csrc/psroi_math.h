@@ -10,11 +10,7 @@
 #pragma once
 #include <cmath>
 
-#ifdef __HIPCC__
-#define MFX_HD __host__ __device__ inline
-#else
-#define MFX_HD inline
-#endif
+#include "hd.h"
 
 namespace mfx {
 namespace psroi {

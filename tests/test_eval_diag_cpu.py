@@ -170,10 +170,18 @@ def test_host_math_want_bits(shim):
     assert (iou1 == np.float32(7.75e8)).all() and (de2 == np.float32(7.75e8)).all()                       # what is not wanted is not written
 
 
+@pytest.fixture(scope="module")
+def decode_shim(tmp_path_factory):
+    from tests import decode_shim as S
+    return S.build(tmp_path_factory.mktemp("decode_shim"))
+
+
 @pytest.mark.parametrize("name", ["b4_m70", "b3_m70_ld50", "b4_m40_ld72"])
-def test_pred_box_is_the_decode_row(shim, name):
+def test_pred_box_is_the_decode_row(shim, decode_shim, name):
     """Box 0 is what the box decode gives for the same pixel under the same class (tests/decode_ref.py, the restatement the decode kernel is
-    pinned to): X, Z, the dimensions and ry at the decode's own bounds; the decode's Y is the bottom centre, box 0's the box centre."""
+    pinned to): X, Z, the dimensions and ry at the decode's own bounds; the decode's Y is the bottom centre, box 0's the box centre.
+    And it IS the row of the decode's host build (tests/shim/decode_row_host.cpp), bit for bit in all eight modes: both run the functions of
+    csrc/box_decode_math.h, compiled without contraction.  Y alone is bounded: the decode stores fl(Y + h / 2)."""
     d = E.case_inputs(name)
     scores, index = E.census_lists(d)
     v = d["gt_rows"][..., 0] != 0
@@ -192,6 +200,10 @@ def test_pred_box_is_the_decode_row(shim, name):
         ry = np.minimum(ry, np.abs(ry - 2 * np.pi)) / np.maximum(1.0, np.abs(det[..., 12]))
         assert (ry[use] <= b[12]).all(), mode
         assert (rel(bx[..., 0, 1], det[..., 10] - det[..., 6] / 2)[use] <= b[10] + b[6]).all(), mode
+        row = decode_shim(dict(d, scores=scores, index=index, img_size=np.array([160, 96]), threshold=C.THRESHOLD), E.yaml_cfg(mode), E.full_layout())[0]
+        for mine, theirs in ((0, "X"), (2, "Z"), (3, "l"), (4, "h"), (5, "w"), (6, "ry")):
+            assert np.array_equal(bx[..., 0, mine][v], row[..., col[theirs]][v]), (mode, theirs)
+        assert (rel(bx[..., 0, 1], row[..., 10].astype(np.float64) - row[..., 6] / 2)[v] <= b[10] + b[6]).all(), mode
 
 
 def settings_cases():
@@ -206,7 +218,7 @@ def settings_cases():
 
 @pytest.mark.parametrize("name,setting", settings_cases())
 def test_pred_box_under_other_settings_and_head_sets(shim, name, setting):
-    """Box 0 (and with it decode_dims, decode_estimates and output_depth of eval_diag_math.h) under the non-yaml head settings and the reduced
+    """Box 0 (and with it decode_dims, decode_estimates and combine of box_decode_math.h) under the non-yaml head settings and the reduced
     head sets PostProcessor accepts with EVAL_DIS_IOUS: against the float64 decode of tests/head_sets_ref.py for the same pixel and class,
     at the bounds the decode kernel is held to under that setting (tests/decode_cfg_ref.py)."""
     from tests import decode_cfg_ref as DC

@@ -100,10 +100,10 @@ SOFT_ULPS = 8                                     # see test_pred_box_is_the_dec
 @pytest.mark.parametrize("name", ["b4_m70", "b3_m70_ld50", "b4_m40_ld72"])
 def test_pred_box_is_the_decode_kernels_row(name):
     """Box 0 EQUALS the row ops.decode_boxes gives for the same pixel listed under the object's class: X, Z, l, h, w and ry bit for bit in the
-    seven modes that pick or average estimates, and the dimensions in every mode.  Under `soft` the two kernels state the same expression
-    ((d0 w0 + d1 w1) + d2 w2) + d3 w3 with w_i = (1 / u_i) / sum, but the compiler contracts its multiply-adds differently in the two
-    contexts (decode_boxes_kernel also forms sigma from the same weights): the depth then differs in its last bits in ~9 % of the rows
-    (measured: 419 of 455, 510 of 560, 788 of 865 values identical).  A fused against an unfused product-sum of four terms differs by at
+    seven modes that pick or average estimates, and the dimensions in every mode.  Under `soft` the two kernels run the same function
+    (csrc/box_decode_math.h bdec::combine: ((d0 w0 + d1 w1) + d2 w2) + d3 w3 with w_i = (1 / u_i) / sum), but the compiler contracts its
+    multiply-adds differently in the two contexts (decode_boxes_kernel also forms sigma from the same weights): the depth then differs in its
+    last bits in ~9 % of the rows (measured: 419 of 455, 510 of 560, 788 of 865 values identical; worst 2.00 ulps).  A fused against an unfused product-sum of four terms differs by at
     most 4 roundings of the depth, and X, Y and ry inherit that relative difference through one product and one sum each: SOFT_ULPS = 8
     float32 ulps of max(1, |value|) bounds it; the worst figure seen is printed.  A restated formula that sums in another order or drops a
     term is off by far more than ulps on these inputs (the four estimates of a row differ by metres).
