@@ -1825,6 +1825,9 @@ static int upsample_bwd_impl(const void* x, const float* w, const void* dy, void
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long total = (long)B * H * W * (C / E);
     const int nrows = B * H;
+    const int dw_items = 4 * f * f * (C / E);
+    // (before the zero fill below: a rejected call leaves dw as it was)
+    if (total > 0 && (dw_items & (dw_items - 1))) return mfx_fail(MFX_ERR_ARG, "upsample_bwd: taps x channel chunks must be a power of two");
     float* part = nullptr;
     int ppb;
     if (workspace && workspace_bytes >= mfx_upsample_bwd_workspace_bytes(B, H, C, f) && total > 0) {
@@ -1836,8 +1839,6 @@ static int upsample_bwd_impl(const void* x, const float* w, const void* dy, void
         ppb = g_opt_deterministic ? nrows : (nrows >= 1024 ? 2 : 1);     // input rows per block: >= ~512 blocks (deterministic: one workgroup)
     }
     if (total == 0) return MFX_OK;
-    const int dw_items = 4 * f * f * (C / E);
-    if (dw_items & (dw_items - 1)) return mfx_fail(MFX_ERR_ARG, "upsample_bwd: taps x channel chunks must be a power of two");
     const size_t dw_smem = dw_items >= 1024 ? 0 : (size_t)1024 * E * sizeof(float);          // [S][items * E], S * items = 1024
     DISPATCH_T(dtype,
         { hipLaunchKernelGGL(upsample_bwd_dx_kernel<float>, TR_GRID(total), dim3(256), 0, st, (const float*)dy, w, (float*)dx, B, H, W, C, f);
