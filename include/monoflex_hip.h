@@ -774,10 +774,33 @@ int mfx_kitti_encode_targets(const mfx_kitti_desc* d, void* stream);
  * The flags travel beside the descriptor so that the mfx_kitti_desc layout and MFX_ABI_VERSION stay as they are. */
 int mfx_kitti_encode_targets_views(const mfx_kitti_desc* d, const int32_t* right, void* stream);
 
+/* The dataset switches of the encoder other than the runs/monoflex.yaml values (non-zero = on).
+ *   consider_outside_objs   DATASETS.CONSIDER_OUTSIDE_OBJS: 0 skips every object whose projected 3D centre is outside the image
+ *                           before the border intersection is tried (kitti.py:381-394): its row stays zero and no status is set.
+ *   adjust_boundary_heatmap INPUT.ADJUST_BOUNDARY_HEATMAP: 0 draws the circular Gaussian of gaussian_radius(box) for truncated
+ *                           objects as well (kitti.py:451-463); status bit 3 cannot occur.
+ *   keypoint_visible_modify INPUT.KEYPOINT_VISIBLE_MODIFY: 0 stores the visibility of each keypoint as computed and derives
+ *                           keypoints_depth_mask from it (kitti.py:403-418).
+ *   heatmap_center_2d       INPUT.HEATMAP_CENTER '2D': the target centre is the rounded centre of the 2D box on the output grid,
+ *                           rounded in the dtype of the box (kitti.py:429-436); offset_3D is still measured from the projected
+ *                           3D centre, and outside objects still need their border intersection (status bits 1, 2 remain).
+ * With heatmap_center_2d, consider_outside_objs and adjust_boundary_heatmap all on, the reference asserts on nearly every
+ * truncated object; the entry computes it all the same and flags status bit 3 there. */
+typedef struct {
+  int32_t consider_outside_objs, adjust_boundary_heatmap, keypoint_visible_modify, heatmap_center_2d;
+} mfx_kitti_encode_cfg;
+/* mfx_kitti_encode_targets_views with these switches. cfg == NULL: the yaml values {1, 1, 1, 0}; right == NULL: all left
+ * views. Like the view flags, the switches travel beside the descriptor: mfx_kitti_desc and MFX_ABI_VERSION are unchanged. */
+int mfx_kitti_encode_targets_cfg(const mfx_kitti_desc* d, const int32_t* right, const mfx_kitti_encode_cfg* cfg, void* stream);
+
 /* uint8 RGB images of different sizes (packed back to back, HWC) -> (B,3,in_h,in_w) float32 NCHW: optional left-right
  * flip, centre zero padding, /255, (x-mean)/std; the padding is zero BEFORE normalisation (kitti.py:218-228). */
 int mfx_kitti_preprocess_u8(const uint8_t* pixels, const int64_t* offsets, const int32_t* img_wh, const int32_t* flip,
                             float* out, int B, int in_w, int in_h, const float* mean3, const float* std3, void* stream);
+/* The same conversion for INPUT.TO_BGR (transforms.py:24-30): mean3 / std3 stay in RGB order and normalise the RGB frame;
+ * output channel c is then source channel 2 - c. */
+int mfx_kitti_preprocess_u8_bgr(const uint8_t* pixels, const int64_t* offsets, const int32_t* img_wh, const int32_t* flip,
+                                float* out, int B, int in_w, int in_h, const float* mean3, const float* std3, void* stream);
 
 /* ---- (5) KITTI AP evaluation on the device -----------------------------------------------------------------------------
  * Replaces the numba CPU loops and the numba.cuda rotated-IoU kernel of the reference's evaluator

@@ -9,6 +9,10 @@
 // and whatever is derived from them by numpy scalar arithmetic stay float32.  Compile with -ffp-contract=off: a fused
 // multiply-add would change float32 results the reference rounds twice.  Right-view samples (kitti.py:232-252) carry a
 // regenerated float32 box, so their flip is a float32 chain; label text is float64 until it is stored.
+//
+// Settings (mfx_kitti_encode_cfg; kitti.py:381-394, 403-418, 429-436, 451-463) reach encode_object by value and are the
+// same for every object of a launch.  The 2D heat-map centre is `bbox_center.round()` in the dtype of the box: float32
+// for a label box, float64 for a projected one, half to even in either.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -22,6 +26,9 @@ namespace kitti {
 
 constexpr double PI = 3.141592653589793;
 constexpr int REC = 14;   // doubles per object record
+
+// runs/monoflex.yaml: outside objects kept, edge heat map, modified keypoint visibility, 3D heat-map centre
+MFX_HD mfx_kitti_encode_cfg yaml_cfg() { return mfx_kitti_encode_cfg{1, 1, 1, 0}; }
 
 MFX_HD void status_or(int32_t* p, int v) {          // objects of one image are encoded by different threads
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -75,6 +82,7 @@ struct BoxStage {          // what the dtype-dependent half of the encoder hands
   float store[4];          // box as stored in "2d_bboxes"
   bool dim_pos;            // (bbox_dim > 0).all()
   int radius;              // circular heat-map radius
+  double round_c[2];       // centre of the box on the output grid, rounded half to even in the dtype of the box
 };
 
 template <typename T>
@@ -91,6 +99,7 @@ MFX_HD BoxStage box_stage(T b0, T b1, T b2, T b3, double truncation, const mfx_k
   s.dim_pos = bw > (T)0 && bh > (T)0;
   s.lo[0] = (double)b0; s.lo[1] = (double)b1; s.hi[0] = (double)b2; s.hi[1] = (double)b3;
   s.store[0] = (float)b0; s.store[1] = (float)b1; s.store[2] = (float)b2; s.store[3] = (float)b3;
+  s.round_c[0] = (double)std::rint((b0 + b2) / (T)2);  s.round_c[1] = (double)std::rint((b1 + b3) / (T)2);      // kitti.py:429,434
   const T r = gaussian_radius<T>(bh, bw);
   const int ri = (int)r;                               // int(): truncation toward zero
   s.radius = ri > 0 ? ri : 0;
@@ -157,7 +166,8 @@ MFX_HD void right_view_box(const double* P, double h, double w, double l, double
 
 // One object of one image: zeroes row i of every per-object field, then fills it unless the reference skips the object.
 // right: the sample is the right-camera view (d.P holds P3): the label's 2D box is replaced by right_view_box() first.
-MFX_HD void encode_object(const mfx_kitti_desc& d, int b, int i, bool right = false) {
+// cfg: the dataset switches; the default is what runs/monoflex.yaml sets.
+MFX_HD void encode_object(const mfx_kitti_desc& d, int b, int i, bool right = false, mfx_kitti_encode_cfg cfg = yaml_cfg()) {
   const int M = d.max_objs;
   const long row = (long)b * M + i;
   d.cls_ids[row] = 0; d.reg_mask[row] = 0; d.trunc_mask[row] = 0; d.reg_weight[row] = 0.f;
@@ -233,6 +243,7 @@ MFX_HD void encode_object(const mfx_kitti_desc& d, int b, int i, bool right = fa
   const bool inside = pc[0] >= 0 && pc[0] <= img_w - 1 && pc[1] >= 0 && pc[1] <= img_h - 1;
   double tpc[2] = {pc[0], pc[1]};
   if (!inside) {
+    if (!cfg.consider_outside_objs) return;                       // kitti.py:393-394: skipped before the intersection, so no status
     const int err = intersect_center(pc, bs.c2d, img_w, img_h, tpc);
     if (err) { status_or(d.status + b, err); return; }          // the reference raises here; flag and drop the object
   }
@@ -241,8 +252,12 @@ MFX_HD void encode_object(const mfx_kitti_desc& d, int b, int i, bool right = fa
   for (int k = 0; k < 10; ++k)
     vis[k] = K2[k][0] >= 0 && K2[k][0] <= img_w - 1 && K2[k][1] >= 0 && K2[k][1] <= img_h - 1 && K3[k][2] > 0;
   bool mv[10];                                                                       // KEYPOINT_VISIBLE_MODIFY (kitti.py:412-414)
-  for (int k = 0; k < 4; ++k) mv[k] = mv[k + 4] = vis[k] || vis[k + 4];
-  mv[8] = mv[9] = vis[8] || vis[9];
+  if (cfg.keypoint_visible_modify) {
+    for (int k = 0; k < 4; ++k) mv[k] = mv[k + 4] = vis[k] || vis[k + 4];
+    mv[8] = mv[9] = vis[8] || vis[9];
+  } else {
+    for (int k = 0; k < 10; ++k) mv[k] = vis[k];                                     // visibility as computed (kitti.py:409-411)
+  }
   const bool dv0 = mv[8] && mv[9], dv1 = mv[0] && mv[2] && mv[4] && mv[6], dv2 = mv[1] && mv[3] && mv[5] && mv[7];
 
   const double down = (double)d.down;
@@ -250,13 +265,14 @@ MFX_HD void encode_object(const mfx_kitti_desc& d, int b, int i, bool right = fa
   const int x_max = (pad_x + img_w - 1) / d.down, y_max = (pad_y + img_h - 1) / d.down;
   const double tx = (tpc[0] + pad_x) / down, ty = (tpc[1] + pad_y) / down;
   const double pcx = (pc[0] + pad_x) / down, pcy = (pc[1] + pad_y) / down;
-  const int tc0 = clampi((int)std::rint(tx), x_min, x_max);                         // np.round: half to even
-  const int tc1 = clampi((int)std::rint(ty), y_min, y_max);
+  // np.round: half to even; HEATMAP_CENTER '2D' takes the rounded box centre instead (kitti.py:433-436)
+  const int tc0 = clampi((int)(cfg.heatmap_center_2d ? bs.round_c[0] : std::rint(tx)), x_min, x_max);
+  const int tc1 = clampi((int)(cfg.heatmap_center_2d ? bs.round_c[1] : std::rint(ty)), y_min, y_max);
   const bool pred_2d = tc0 >= bs.lo[0] && tc1 >= bs.lo[1] && tc0 <= bs.hi[0] && tc1 <= bs.hi[1];
   if (!(bs.dim_pos && tc0 >= 0 && tc0 <= out_w - 1 && tc1 >= 0 && tc1 <= out_h - 1)) return;
 
   int rx, ryy, circular;
-  if (!inside) {                                                                     // boundary heat-map (kitti.py:444-450)
+  if (!inside && cfg.adjust_boundary_heatmap) {                                      // boundary heat-map (kitti.py:451-458)
     const double a0 = tc0 - bs.lo[0], a1 = bs.hi[0] - tc0, c0 = tc1 - bs.lo[1], c1 = bs.hi[1] - tc1;
     const double bw = a0 < a1 ? a0 : a1, bh = c0 < c1 ? c0 : c1;
     rx = (int)(bw * d.edge_ratio); ryy = (int)(bh * d.edge_ratio);
@@ -356,8 +372,10 @@ MFX_HD float heat_pixel(const mfx_kitti_desc& d, int b, int cls, int y, int x) {
 }
 
 // Output pixel (b, y, x) of the network input, all three channels (data/transforms/transforms.py:15-31).
+// to_bgr (INPUT.TO_BGR, transforms.py:24-30): normalised in RGB order, then output channel c is source channel 2 - c.
 MFX_HD void preprocess_pixel(const uint8_t* pixels, const int64_t* offsets, const int32_t* img_wh, const int32_t* flip,
-                             float* out, int b, int y, int x, int in_w, int in_h, const float* mean, const float* stdv) {
+                             float* out, int b, int y, int x, int in_w, int in_h, const float* mean, const float* stdv,
+                             bool to_bgr = false) {
   const int img_w = img_wh[b * 2], img_h = img_wh[b * 2 + 1];
   const int pad_x = (in_w - img_w) / 2, pad_y = (in_h - img_h) / 2;
   const int sy = y - pad_y;
@@ -369,7 +387,7 @@ MFX_HD void preprocess_pixel(const uint8_t* pixels, const int64_t* offsets, cons
   float* o = out + (long)b * 3 * plane + (long)y * in_w + x;
   for (int c = 0; c < 3; ++c) {
     const float v = in ? (float)src[c] / 255.f : 0.f;
-    o[c * plane] = (v - mean[c]) / stdv[c];
+    o[(to_bgr ? 2 - c : c) * plane] = (v - mean[c]) / stdv[c];
   }
 }
 

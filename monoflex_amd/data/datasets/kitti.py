@@ -58,8 +58,6 @@ class KITTIDataset(torch.utils.data.Dataset):
         self.params = EncodeParams.from_cfg(cfg)
         self.flip_p = float(cfg.INPUT.AUG_PARAMS[0][0]) if (is_train and augment) else 0.0      # augmentations/__init__.py:15-23
         self.pixel_mean, self.pixel_std = tuple(cfg.INPUT.PIXEL_MEAN), tuple(cfg.INPUT.PIXEL_STD)
-        if cfg.INPUT.TO_BGR:
-            raise NotImplementedError("INPUT.TO_BGR is not implemented in this build")
         self.input_width, self.input_height = self.params.in_w, self.params.in_h
         self.down_ratio = self.params.down
         self.output_width, self.output_height = self.input_width // self.down_ratio, self.input_height // self.down_ratio

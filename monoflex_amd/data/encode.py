@@ -1,4 +1,4 @@
-"""Device-side sample encoding: the ctypes front of mfx_kitti_encode_targets[_views] / mfx_kitti_preprocess_u8.
+"""Device-side sample encoding: the ctypes front of mfx_kitti_encode_targets[_views|_cfg] / mfx_kitti_preprocess_u8[_bgr].
 
 Replaces the numeric half of the reference's KITTIDataset.__getitem__ (data/datasets/kitti.py:231-525), its flip
 augmentation (data/augmentations/augmentations.py:33-78) and ToTensor+Normalize (data/transforms/transforms.py:15-31):
@@ -46,30 +46,57 @@ STATUS_MESSAGES = {1: "more objects of the detect classes than DATASETS.MAX_OBJE
 
 
 class EncodeParams:
-    """The dataset settings the encoder depends on (reference KITTIDataset.__init__, kitti.py:60-98)."""
+    """The dataset settings the encoder depends on (reference KITTIDataset.__init__, kitti.py:60-98). The defaults are the
+    runs/monoflex.yaml values. consider_outside_objs / adjust_boundary_heatmap / keypoint_visible_modify / heatmap_center are
+    DATASETS.CONSIDER_OUTSIDE_OBJS, INPUT.ADJUST_BOUNDARY_HEATMAP, INPUT.KEYPOINT_VISIBLE_MODIFY, INPUT.HEATMAP_CENTER;
+    to_bgr is INPUT.TO_BGR and concerns the frames only."""
 
     def __init__(self, in_w=1280, in_h=384, down=4, max_objs=40, num_classes=3, filter_annos=(0.9, 20.0), filter_enable=True,
-                 edge_ratio=0.5):
+                 edge_ratio=0.5, consider_outside_objs=True, adjust_boundary_heatmap=True, keypoint_visible_modify=True,
+                 heatmap_center="3D", to_bgr=False):
         self.in_w, self.in_h, self.down, self.max_objs, self.num_classes = in_w, in_h, down, max_objs, num_classes
         self.filter_trunc = float(filter_annos[0]) if filter_enable else -1.0
         self.filter_size = float(filter_annos[1])
         self.edge_ratio = float(edge_ratio)
+        if heatmap_center not in ("3D", "2D"):
+            raise ValueError("INPUT.HEATMAP_CENTER is '3D' or '2D', got %r" % (heatmap_center,))
+        self.consider_outside_objs, self.adjust_boundary_heatmap = bool(consider_outside_objs), bool(adjust_boundary_heatmap)
+        self.keypoint_visible_modify, self.heatmap_center, self.to_bgr = bool(keypoint_visible_modify), heatmap_center, bool(to_bgr)
+        if heatmap_center == "2D" and self.consider_outside_objs and self.adjust_boundary_heatmap:
+            raise NotImplementedError(
+                "INPUT.HEATMAP_CENTER '2D' with DATASETS.CONSIDER_OUTSIDE_OBJS and INPUT.ADJUST_BOUNDARY_HEATMAP both on: the "
+                "reference draws the edge heat map around a centre in the middle of the box, where both radii are positive, and "
+                "fails its assertion on all but the smallest truncated objects; switch one of the two off")
+
+    def is_yaml(self):
+        """True when the four encoder switches have their runs/monoflex.yaml values (the plain entries serve those)."""
+        return (self.consider_outside_objs and self.adjust_boundary_heatmap and self.keypoint_visible_modify
+                and self.heatmap_center == "3D")
+
+    def encode_cfg(self):
+        return L.KittiEncodeCfg(int(self.consider_outside_objs), int(self.adjust_boundary_heatmap),
+                                int(self.keypoint_visible_modify), int(self.heatmap_center == "2D"))
 
     @classmethod
     def from_cfg(cls, cfg):
+        """Refuses, with the reason, what the reference itself cannot run (it raises while encoding) and the one orientation
+        code that is not built; the '2D'-centre edge heat map is refused by the constructor."""
         unsupported = []
-        if cfg.INPUT.HEATMAP_CENTER != "3D": unsupported.append("INPUT.HEATMAP_CENTER != '3D'")
-        if not cfg.DATASETS.CONSIDER_OUTSIDE_OBJS: unsupported.append("DATASETS.CONSIDER_OUTSIDE_OBJS False")
-        if cfg.INPUT.APPROX_3D_CENTER != "intersect": unsupported.append("INPUT.APPROX_3D_CENTER != 'intersect'")
-        if not cfg.INPUT.ADJUST_BOUNDARY_HEATMAP: unsupported.append("INPUT.ADJUST_BOUNDARY_HEATMAP False")
-        if not cfg.INPUT.KEYPOINT_VISIBLE_MODIFY: unsupported.append("INPUT.KEYPOINT_VISIBLE_MODIFY False")
-        if cfg.INPUT.ORIENTATION != "multi-bin" or cfg.INPUT.ORIENTATION_BIN_SIZE != 4:
-            unsupported.append("INPUT.ORIENTATION other than 4-bin 'multi-bin'")
+        if cfg.INPUT.APPROX_3D_CENTER != "intersect":
+            unsupported.append("INPUT.APPROX_3D_CENTER != 'intersect' (the reference raises NotImplementedError for any other mode)")
+        if cfg.INPUT.ORIENTATION == "head-axis":
+            unsupported.append("INPUT.ORIENTATION 'head-axis' (the reference writes eight values into a three-wide row and fails on "
+                               "the first kept object)")
+        elif cfg.INPUT.ORIENTATION != "multi-bin":
+            unsupported.append("INPUT.ORIENTATION %r (only 'multi-bin' is encoded)" % (cfg.INPUT.ORIENTATION,))
+        if cfg.INPUT.ORIENTATION_BIN_SIZE != 4:
+            unsupported.append("INPUT.ORIENTATION_BIN_SIZE != 4 (the encoder and the heads are built for four bins)")
         if unsupported:
-            raise NotImplementedError("the device target encoder implements the runs/monoflex.yaml settings only: " + "; ".join(unsupported))
+            raise NotImplementedError("the device target encoder does not serve: " + "; ".join(unsupported))
         return cls(cfg.INPUT.WIDTH_TRAIN, cfg.INPUT.HEIGHT_TRAIN, cfg.MODEL.BACKBONE.DOWN_RATIO, cfg.DATASETS.MAX_OBJECTS,
                    len(cfg.DATASETS.DETECT_CLASSES), tuple(cfg.DATASETS.FILTER_ANNOS), bool(cfg.DATASETS.FILTER_ANNO_ENABLE),
-                   cfg.INPUT.HEATMAP_RATIO)
+                   cfg.INPUT.HEATMAP_RATIO, bool(cfg.DATASETS.CONSIDER_OUTSIDE_OBJS), bool(cfg.INPUT.ADJUST_BOUNDARY_HEATMAP),
+                   bool(cfg.INPUT.KEYPOINT_VISIBLE_MODIFY), cfg.INPUT.HEATMAP_CENTER, bool(cfg.INPUT.TO_BGR))
 
     def dims(self):
         out_w, out_h = self.in_w // self.down, self.in_h // self.down
@@ -128,7 +155,8 @@ def _alloc_outputs(B, dims, device):
 
 class PreparedEncode:
     """One batch ready to launch: inputs uploaded, outputs allocated, descriptor filled. `launch()` enqueues the two encoder
-    kernels on the current stream and may be repeated (the timing tools do); `out` is {field: (B, ...) device tensor}."""
+    kernels on the current stream and may be repeated (the timing tools do); `out` is {field: (B, ...) device tensor}.
+    With every switch of `params` at its yaml value the plain entries are called; otherwise mfx_kitti_encode_targets_cfg."""
 
     def __init__(self, records, Ps, sizes, flips, params, device, rights=None):
         self.lib, self.device = L.load(), device
@@ -146,11 +174,15 @@ class PreparedEncode:
             setattr(d, member, self.out[name].data_ptr())
         d.B, d.max_objs, d.in_w, d.in_h, d.down, d.num_classes = B, params.max_objs, params.in_w, params.in_h, params.down, params.num_classes
         d.filter_trunc, d.filter_size, d.edge_ratio = params.filter_trunc, params.filter_size, params.edge_ratio
+        self.cfg = None if params.is_yaml() else params.encode_cfg()
 
     def launch(self):
         with torch.cuda.device(self.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            if self.right is None:
+            if self.cfg is not None:
+                L.check(self.lib.mfx_kitti_encode_targets_cfg(ctypes.byref(self.desc), None if self.right is None else self.right.data_ptr(),
+                                                              ctypes.byref(self.cfg), stream), "mfx_kitti_encode_targets_cfg")
+            elif self.right is None:
                 L.check(self.lib.mfx_kitti_encode_targets(ctypes.byref(self.desc), stream), "mfx_kitti_encode_targets")
             else:
                 L.check(self.lib.mfx_kitti_encode_targets_views(ctypes.byref(self.desc), self.right.data_ptr(), stream),
@@ -182,7 +214,8 @@ def check_status(status):
 
 def preprocess_images(frames, flips, params, device, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """List of (h_i, w_i, 3) uint8 RGB frames (numpy) -> (B, 3, in_h, in_w) float32 device tensor: flip, centre zero padding,
-    /255, (x - mean) / std (kitti.py:218-228, transforms.py:15-31; INPUT.TO_BGR False)."""
+    /255, (x - mean) / std (kitti.py:218-228, transforms.py:15-31). params.to_bgr (INPUT.TO_BGR): the normalised channels
+    are then stored in B, G, R order (mfx_kitti_preprocess_u8_bgr); mean / std stay in RGB order."""
     if torch.device(device).type != "cuda":
         raise RuntimeError("preprocess_images runs on the GPU (HIP kernel); there is no CPU fallback")
     lib = L.load()
@@ -209,7 +242,8 @@ def preprocess_images(frames, flips, params, device, mean=(0.485, 0.456, 0.406),
     m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream().cuda_stream
-        L.check(lib.mfx_kitti_preprocess_u8(pixels.data_ptr(), meta["offsets"].data_ptr(), meta["img_wh"].data_ptr(),
-                                            meta["flip"].data_ptr(), out.data_ptr(), B, params.in_w, params.in_h, m3, s3,
-                                            ctypes.c_void_p(stream)), "mfx_kitti_preprocess_u8")
+        name = "mfx_kitti_preprocess_u8_bgr" if params.to_bgr else "mfx_kitti_preprocess_u8"
+        L.check(getattr(lib, name)(pixels.data_ptr(), meta["offsets"].data_ptr(), meta["img_wh"].data_ptr(),
+                                   meta["flip"].data_ptr(), out.data_ptr(), B, params.in_w, params.in_h, m3, s3,
+                                   ctypes.c_void_p(stream)), name)
     return out

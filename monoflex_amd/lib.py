@@ -70,6 +70,12 @@ class KittiDesc(ctypes.Structure):
         [(n, ctypes.c_double) for n in ("filter_trunc", "filter_size", "edge_ratio")]
 
 
+class KittiEncodeCfg(ctypes.Structure):
+    """mfx_kitti_encode_cfg: the encoder's dataset switches, beside the descriptor."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("consider_outside_objs", "adjust_boundary_heatmap", "keypoint_visible_modify",
+                                              "heatmap_center_2d")]
+
+
 class KittiEvalDesc(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("gt", "dt", "gt_off", "dt_off", "pair_off", "classes", "min_overlaps", "overlaps", "tp_scores",
                                         "num_valid_gt", "thresholds", "num_thresholds", "pr")] + \
@@ -213,7 +219,9 @@ SYMBOLS = {
     "mfx_eval_diagnostics": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, ctypes.POINTER(DecodeCfg), ctypes.POINTER(HeadLayout), _I, _P, _P, _P, _P]),
     "mfx_kitti_encode_targets": (_I, [ctypes.POINTER(KittiDesc), _P]),
     "mfx_kitti_encode_targets_views": (_I, [ctypes.POINTER(KittiDesc), _P, _P]),
+    "mfx_kitti_encode_targets_cfg": (_I, [ctypes.POINTER(KittiDesc), _P, ctypes.POINTER(KittiEncodeCfg), _P]),
     "mfx_kitti_preprocess_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.POINTER(c_float), ctypes.POINTER(c_float), _P]),
+    "mfx_kitti_preprocess_u8_bgr": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.POINTER(c_float), ctypes.POINTER(c_float), _P]),
     "mfx_kitti_eval_overlaps": (_I, [ctypes.POINTER(KittiEvalDesc), _P]),
     "mfx_kitti_eval_match_pass1": (_I, [ctypes.POINTER(KittiEvalDesc), _P]),
     "mfx_kitti_eval_thresholds": (_I, [ctypes.POINTER(KittiEvalDesc), _P, _P]),

@@ -1,7 +1,9 @@
 """Timing of the device input pipeline (one batch of B KITTI samples) next to the CPU restatement of the reference's
 per-sample __getitem__ arithmetic. Prints one JSON line; HBM roofline for the frame kernel (bytes = frames in + fp32 out).
 --right-fraction F: that share of the batch are right-camera samples (DATASETS.USE_RIGHT_IMAGE: P3, 2D boxes regenerated from
-the 3D corners through mfx_kitti_encode_targets_views); 0 = the plain entry, as before."""
+the 3D corners through mfx_kitti_encode_targets_views); 0 = the plain entry, as before.
+--default-settings: encode with the config/defaults.py data settings (outside objects discarded, circular heat maps only, raw
+keypoint visibility, no annotation filter) through mfx_kitti_encode_targets_cfg; absent = the runs/monoflex.yaml settings, as before."""
 import argparse
 import json
 import os
@@ -21,8 +23,10 @@ ap.add_argument("--batch", type=int, default=8)
 ap.add_argument("--objects", type=int, default=12)
 ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--right-fraction", type=float, default=0.0)
+ap.add_argument("--default-settings", action="store_true")
 a = ap.parse_args()
-params = E.EncodeParams()
+params = E.EncodeParams(consider_outside_objs=False, adjust_boundary_heatmap=False, keypoint_visible_modify=False,
+                        filter_enable=False) if a.default_settings else E.EncodeParams()
 labels = [S.synthetic_kitti_labels(100 + i, 1242, 375, a.objects) for i in range(a.batch)]
 recs = [KU.read_label_records(l, ("Car", "Pedestrian", "Cyclist")) for l in labels]
 frames = [np.random.RandomState(i).randint(0, 256, (375, 1242, 3)).astype(np.uint8) for i in range(a.batch)]
@@ -99,7 +103,7 @@ while time.perf_counter() - t0 < 5.0:
 cpu_ms = (time.perf_counter() - t0) / n_cpu * 1e3
 print(json.dumps({"what": "KITTI input pipeline, batch %d x 1242x375, %d label lines/image" % (a.batch, a.objects),
                   "gpu_ms_per_batch_incl_host_packing_and_h2d": round(wall_ms, 3), "gpu_images_per_s": round(a.batch / wall_ms * 1e3, 1),
-                  "right_view_samples": n_right, "encode_kernels_ms": round(encode_ms, 4),
+                  "right_view_samples": n_right, "settings": "defaults" if a.default_settings else "yaml", "encode_kernels_ms": round(encode_ms, 4),
                   "frame_kernel_ms": round(frame_ms, 4), "frame_kernel_GBps": round(bytes_frame / frame_ms / 1e6, 1),
                   "frame_kernel_hbm_frac": round(bytes_frame / frame_ms / 1e6 / 8000, 3),
                   "cpu_port_ms_per_image": round(cpu_ms, 3), "cpu_port_images_per_s_1core": round(1e3 / cpu_ms, 1)}))
