@@ -303,6 +303,11 @@ typedef struct {
     const void* w1_32; const void* w2_32;
 } mfx_heads_desc;
 int mfx_heads_fused(const mfx_heads_desc* d, void* stream);
+/* The same with the trunk activation named: `act` = MFX_ACT_LEAKY (InPlaceABN's leaky_relu(0.01); what mfx_heads_fused passes) or MFX_ACT_RELU
+ * (MODEL.INPLACE_ABN False: BatchNorm2d + ReLU, max(z, +0)); anything else MFX_ERR_UNSUPPORTED.  Like the encoder's view flags and switches the
+ * activation travels beside the descriptor: mfx_heads_desc and MFX_ABI_VERSION stay as they are.  The mfx_*_act entry points below follow the
+ * same rule for the head trunks of the edge chain, the sparse heads and the Gram heads. */
+int mfx_heads_fused_act(const mfx_heads_desc* d, int act, void* stream);
 
 /* Edge fusion tail (detector_predictor.py:152-158): out[b, y, x, ch_off + c] += v[b][i][c] for the
  * first edge_len[b] border points i of image b.  v: fp32 [B][L][ldv], edge_xy: int32 [B][L][2]. */
@@ -331,6 +336,8 @@ typedef struct {
 } mfx_edge_chain_desc;
 /* MFX_ERR_ARG: null pointer or bad sizes; MFX_ERR_UNSUPPORTED: anything but MFX_BF16 / MFX_F16, C = 64, head_conv = 256, ksize = 3 */
 int mfx_edge_chain(const mfx_edge_chain_desc* d, void* stream);
+/* trunk row(p) = act(BN(conv3x3(x))) with act = MFX_ACT_LEAKY (mfx_edge_chain) or MFX_ACT_RELU */
+int mfx_edge_chain_act(const mfx_edge_chain_desc* d, int act, void* stream);
 /* 1 if mfx_edge_chain takes this configuration and option "edge_chain" is on (the caller then replaces its five conv launches by it) */
 int mfx_edge_chain_applies(const mfx_edge_chain_desc* d);
 
@@ -670,6 +677,9 @@ typedef struct mfx_head_sparse_desc {
     void* arena; size_t arena_bytes;
 } mfx_head_sparse_desc;
 int mfx_head_sparse_fwd(const mfx_head_sparse_desc* d, void* stream);
+/* the trunk activation named (MFX_ACT_LEAKY = the plain entry points, MFX_ACT_RELU: derivative 1 for z > 0, 0 otherwise, 0 at z == 0) */
+int mfx_head_sparse_fwd_act(const mfx_head_sparse_desc* d, int act, void* stream);
+int mfx_head_sparse_bwd_act(const mfx_head_sparse_desc* d, int act, void* stream);
 /* The same regression branches WITHOUT their dense trunk maps: batch statistics from the patch Gram matrix of the shared 64-channel input,
  * trunk values at the object rows (and, for branch `extra_branch`, at `Ne` edge-sequence pixels) only -- csrc/gram_heads.hip, the hand-written
  * forward and backward of monoflex_amd/gram_heads.py (reference model/head/detector_predictor.py:125-165).  One descriptor for the whole node;
@@ -708,6 +718,7 @@ typedef struct mfx_gram_desc {
     float* dAf; float* dArows; void* dx; const long long* ring_inv; const long long* ring_idx; const float* dwo; const float* dwe;
 } mfx_gram_desc;
 int mfx_gram_heads(const mfx_gram_desc* d, int phase, void* stream);
+int mfx_gram_heads_act(const mfx_gram_desc* d, int phase, int act, void* stream);      /* MFX_ACT_LEAKY (= mfx_gram_heads) or MFX_ACT_RELU; read by phases 2 and 3 */
 int mfx_head_sparse_bwd(const mfx_head_sparse_desc* d, void* stream);
 /* Batch statistics of a train-mode BN without applying it: mean / rstd (C floats each), running statistics and
  * num_batches_tracked updated as mfx_bn_train_fwd does; `scratch` as there (zero before, zero after). */

@@ -1110,17 +1110,30 @@ class ObjectLossFn(Function):
         return dreg, None, None, None
 
 
+def trunk_act(norm):
+    """The activation that follows a head trunk's norm holder: a torch `_BatchNorm` (MODEL.INPLACE_ABN False; SyncBatchNorm after torch's converter)
+    is followed by ReLU, the InPlaceABN holder carries its own leaky_relu(0.01) -- the reference's two trunk forms (detector_predictor.py:53-58)."""
+    return L.ACT_RELU if isinstance(norm, torch.nn.modules.batchnorm._BatchNorm) else L.ACT_LEAKY
+
+
 @_device_guarded
 class SparseRegHeadsFn(Function):
     """Regression branches of the training step at the object centres only (csrc/head_sparse.hip): per branch the dense trunk
     conv output y (B,H,W,256), its ABN holder and the stacked 1x1 heads (w2 (k,256[,1,1]), b2 (k)) -> out fp32 [N][ld_out], row n
     = object row n of `rows`, branch i at columns [offs[i], offs[i]+k_i).  The ABN's batch statistics are taken over the dense
-    map (running statistics and num_batches_tracked move as in bn_act); backward is one dense pass per branch."""
+    map (running statistics and num_batches_tracked move as in bn_act); backward is one dense pass per branch.  The activation is
+    `trunk_act` of the holders (one for all branches).  The statistics are RANK-LOCAL (mfx_bn_train_stats): a synchronised norm must
+    not come here -- the predictor sends those through the Gram or the dense form."""
 
     @staticmethod
     def forward(ctx, rows, abns, offs, ld_out, stats_done, *ts):
         nb = len(abns)
         ys, gammas, betas, w2s, b2s = (ts[i * nb:(i + 1) * nb] for i in range(5))
+        act = trunk_act(abns[0])
+        if any(trunk_act(a) != act for a in abns):
+            raise NotImplementedError("SparseRegHeadsFn: one activation for all branches")
+        if any(_sync_group(bool(getattr(a, 'sync_bn', False)) or isinstance(a, torch.nn.SyncBatchNorm)) is not None for a in abns):
+            raise NotImplementedError("SparseRegHeadsFn takes rank-local batch statistics: a synchronised norm goes through gram_reg_heads or bn_act")
         ys = [_c(y) for y in ys]
         y0 = ys[0]
         B, H, W, C = y0.shape
@@ -1147,15 +1160,15 @@ class SparseRegHeadsFn(Function):
             keep += [g32, b32, w2, b2]
         out = torch.zeros(rows.shape[0], ld_out, dtype=torch.float32, device=y0.device)
         d.out = out.data_ptr()
-        L.check(lib_.mfx_head_sparse_fwd(ctypes.byref(d), _stream()), "mfx_head_sparse_fwd")
+        L.check(lib_.mfx_head_sparse_fwd_act(ctypes.byref(d), act, _stream()), "mfx_head_sparse_fwd_act")
         ctx.save_for_backward(rows, stats, *ys, *[t for t in keep if t is not None])
-        ctx.meta = (nb, offs, ld_out, [w.shape for w in w2s], [b is not None for b in b2s], [w.shape[0] for w in w2s])
+        ctx.meta = (nb, offs, ld_out, [w.shape for w in w2s], [b is not None for b in b2s], [w.shape[0] for w in w2s], act)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
-        nb, offs, ld_out, wshapes, has_b, ks = ctx.meta
+        nb, offs, ld_out, wshapes, has_b, ks, act = ctx.meta
         saved = list(ctx.saved_tensors)
         rows, stats = saved[0], saved[1]
         ys = saved[2:2 + nb]
@@ -1187,7 +1200,7 @@ class SparseRegHeadsFn(Function):
             d.k[i], d.out_off[i] = k, offs[i]
             d.sums[i], d.dw2[i], d.db2[i], d.dx[i] = sm.data_ptr(), dw.data_ptr(), db.data_ptr(), dx.data_ptr()
             dxs.append(dx); sums.append(sm); dw2s.append(dw.view(wshapes[i])); db2s.append(db if has_b[i] else None)
-        L.check(L.load().mfx_head_sparse_bwd(ctypes.byref(d), _stream()), "mfx_head_sparse_bwd")
+        L.check(L.load().mfx_head_sparse_bwd_act(ctypes.byref(d), act, _stream()), "mfx_head_sparse_bwd_act")
         dgammas = [sm[C:] for sm in sums]
         dbetas = [sm[:C] for sm in sums]
         return (None, None, None, None, None, *dxs, *dgammas, *dbetas, *dw2s, *db2s)

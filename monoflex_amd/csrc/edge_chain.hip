@@ -1,6 +1,6 @@
 // The conv chain of the edge fusion (detector_predictor.py:111-119,152-158) as ONE kernel: at the border points of the feature map, per fusion
 // branch (class, 3d_offset)
-//   trunk   3x3 64 -> 256 + folded ABN + LeakyReLU(0.01)                      (rounded to the activation type)
+//   trunk   3x3 64 -> 256 + folded ABN + LeakyReLU(0.01) (or BN + ReLU: mfx_edge_chain_act)                    (rounded to the activation type)
 //   Conv1d  k = 3 along the point sequence, replicate padded, 256 -> 256 + folded BN1d (+ ReLU)   (rounded to the activation type)
 //   1x1     256 -> c (<= 4) + bias                                                            (fp32)
 // which mfx_conv2d_nhwc runs as five launches (row-map trunk for both branches, then two convs per branch) with the two intermediates in memory.
@@ -102,7 +102,8 @@ __device__ __forceinline__ void chain_epilogue(const f32x4 (&acc)[4][4], char* d
     }
 }
 
-template <typename T>
+// TACT: the trunk's activation (ACT_LEAKY: InPlaceABN; ACT_RELU: BatchNorm2d + ReLU), the expressions of mfx_conv2d_nhwc's epilogue
+template <typename T, int TACT>
 __global__ __launch_bounds__(256) void edge_chain_kernel(EdgeChainArgs a) {
     using namespace ec;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256) void edge_chain_kernel(EdgeChainArgs a) {
     chain_gemm<T, NK1, G_ROW>(acc, ring, w1, [&](int ks) { return Gs + frag * G_ROW + ks * 64 + kq16; });
     const u32x4* w2 = reinterpret_cast<const u32x4*>(a.w_conv) + (size_t)(br * 16 + wave * 4) * NK2 * 64 + lane;
     ring_fill<NK2>(ring, w2);                 // (the Conv1d's first weights travel under the epilogue)
-    chain_epilogue<T, ACT_LEAKY>(acc, Ts, a.scale_trunk + br * HC, a.shift_trunk + br * HC, wave * 64, lane);
+    chain_epilogue<T, TACT>(acc, Ts, a.scale_trunk + br * HC, a.shift_trunk + br * HC, wave * 64, lane);
     __syncthreads();                          // trunk complete; every wave is done with the gathered input
 
     // ---- Conv1d: tile row i = position p0 + i, taps = trunk rows i, i + 1, i + 2; K = (tap, channel)
@@ -187,8 +188,8 @@ static bool edge_chain_supported(const mfx_edge_chain_desc* d) {
     return (d->dtype == MFX_BF16 || d->dtype == MFX_F16) && d->C == ec::CIN && d->head_conv == ec::HC && d->ksize == 3;
 }
 
-template <typename T> static int launch_edge_chain(const EdgeChainArgs& a, hipStream_t st) {
-    auto k = edge_chain_kernel<T>;
+template <typename T, int TACT> static int launch_edge_chain(const EdgeChainArgs& a, hipStream_t st) {
+    auto k = edge_chain_kernel<T, TACT>;
     static bool attr_set = false;
     if (!attr_set) {
         MFX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, ec::SMEM));
@@ -205,12 +206,15 @@ using namespace mfx;
 
 extern "C" int mfx_edge_chain_applies(const mfx_edge_chain_desc* d) { return (d && g_opt_edge_chain != 0 && edge_chain_supported(d)) ? 1 : 0; }
 
-extern "C" int mfx_edge_chain(const mfx_edge_chain_desc* d, void* stream) {
+extern "C" int mfx_edge_chain(const mfx_edge_chain_desc* d, void* stream) { return mfx_edge_chain_act(d, MFX_ACT_LEAKY, stream); }
+
+extern "C" int mfx_edge_chain_act(const mfx_edge_chain_desc* d, int act, void* stream) {
     if (!d || !d->x || !d->edge_xy || !d->w_trunk || !d->scale_trunk || !d->shift_trunk || !d->w_conv || !d->scale_conv || !d->shift_conv ||
         !d->w_out || !d->bias_out || !d->out)
         return mfx_fail(MFX_ERR_ARG, "edge_chain: null pointer");
     if (d->dtype != MFX_BF16 && d->dtype != MFX_F16) return mfx_fail(MFX_ERR_UNSUPPORTED, "edge_chain: bf16 or fp16 activations only");
     if (!edge_chain_supported(d)) return mfx_fail(MFX_ERR_UNSUPPORTED, "edge_chain: built for 64 feature channels, 256 head channels and a k = 3 Conv1d");
+    if (act != MFX_ACT_LEAKY && act != MFX_ACT_RELU) return mfx_fail(MFX_ERR_UNSUPPORTED, "edge_chain: the trunk activation is MFX_ACT_LEAKY or MFX_ACT_RELU");
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->L < 0) return mfx_fail(MFX_ERR_ARG, "edge_chain: bad B / H / W / L");
     if (d->B > 65535) return mfx_fail(MFX_ERR_UNSUPPORTED, "edge_chain: more than 65535 images");
     if (d->L == 0) return MFX_OK;
@@ -222,5 +226,6 @@ extern "C" int mfx_edge_chain(const mfx_edge_chain_desc* d, void* stream) {
     a.B = d->B; a.H = d->H; a.W = d->W; a.L = d->L; a.relu = d->relu ? 1 : 0;
     ++g_cnt_edge_chain;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return d->dtype == MFX_BF16 ? launch_edge_chain<bf16_t>(a, st) : launch_edge_chain<half_t>(a, st);
+    if (act == MFX_ACT_RELU) return d->dtype == MFX_BF16 ? launch_edge_chain<bf16_t, ACT_RELU>(a, st) : launch_edge_chain<half_t, ACT_RELU>(a, st);
+    return d->dtype == MFX_BF16 ? launch_edge_chain<bf16_t, ACT_LEAKY>(a, st) : launch_edge_chain<half_t, ACT_LEAKY>(a, st);
 }

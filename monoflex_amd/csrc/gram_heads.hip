@@ -9,7 +9,7 @@
 // as torch ops differentiated by torch.autograd.grad -- 321 small `at::native` launches and 16 Tensile GEMMs per step, 2.1 ms of the 19.4 ms
 // step.  Here the same arithmetic is ~20 kernels of this file plus the library's own weight-gradient / conv launches, with the
 // backward written out by hand:
-//     z = y sc + sh,  act = leaky(z),  out = act W2^T + b2;     sc = gamma rstd,  sh = beta - mean sc,  rstd = (var + eps)^-1/2,
+//     z = y sc + sh,  act = leaky(z) (or relu(z): mfx_gram_heads_act),  out = act W2^T + b2;     sc = gamma rstd,  sh = beta - mean sc,  rstd = (var + eps)^-1/2,
 //     mean = s1 / M,  var = s2 / M - mean^2,                      s1 = W m,  s2_c = w_c^T G w_c
 //     d sc_tot = d sc - mean d sh;  d gamma = d sc_tot rstd;  d beta = d sh;  d var = -1/2 d sc_tot gamma rstd^3 (0 where the clamp at 0 is active)
 //     d mean = -sc d sh - 2 mean d var;  d s1 = d mean / M;  d s2 = d var / M
@@ -23,6 +23,7 @@
 #include "common.h"
 #include "err.h"
 #include "fill.h"
+#include "head_act.h"
 #include <algorithm>
 
 namespace mfx {
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(256) void gram_finalize_kernel(GD d) {
 // Workgroup = 16 rows x (FN * 64) columns, wave w = FN 16-column blocks.  MODE 0: out (fp32) = alpha * sum.
 // MODE 1 (trunk rows): Y (fp32) = sum, act = leaky(Y sc + sh) as fp32 (objects) or in the activation type (edge rows).
 struct RowGemm { const void* A; const void* Alo; const void* Bm; float* out; void* act; const float* sc; const float* sh; const float* alpha;
-                 int R, K, lda, ldb, ldo, ncols, act16; float alpha_mul; };
+                 int R, K, lda, ldb, ldo, ncols, act16; float alpha_mul, slope /* MODE 1: head_act.h */; };
 
 template <typename T, int FN, int MODE>
 __global__ __launch_bounds__(256) void gram_rowgemm_kernel(RowGemm g) {
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(256) void gram_rowgemm_kernel(RowGemm g) {
             else {
                 g.out[(size_t)rr * g.ldo + n] = v;
                 const float z = v * g.sc[n] + g.sh[n];
-                const float a_ = z > 0.f ? z : 0.01f * z;
+                const float a_ = head_act(z, g.slope);
                 if (g.act16) g_st<T>(reinterpret_cast<T*>(g.act) + (size_t)rr * g.ldo + n, a_);
                 else reinterpret_cast<float*>(g.act)[(size_t)rr * g.ldo + n] = a_;
             }
@@ -281,7 +282,7 @@ template <typename T> __device__ __forceinline__ void g_split(float v, T* hi, T*
 // object rows (blockIdx.x < nchunk_obj) and edge rows of branch `extra_branch`: thread = trunk channel.
 //   d act -> d z -> d y = d z sc (hi + lo halves);  d sc += d z y,  d sh += d z;  d W2 += d out (x) act,  d b2 += d out
 template <typename T>
-__global__ __launch_bounds__(256) void gram_rows_bwd_kernel(GD d, int rpb, int nchunk_obj, int rpb_e) {
+__global__ __launch_bounds__(256) void gram_rows_bwd_kernel(GD d, int rpb, int nchunk_obj, int rpb_e, float slope) {
     const int CH = d.nbranch * GT;
     const int c = threadIdx.x, b = blockIdx.y, ch = b * GT + c;
     const float sc = d.stat[3 * CH + ch], sh = d.stat[4 * CH + ch];
@@ -297,12 +298,12 @@ __global__ __launch_bounds__(256) void gram_rows_bwd_kernel(GD d, int rpb, int n
             float gy = 0.f;
             if (d.rows[(size_t)n * G_ROW] > 0.f) {
                 const float y = d.Y[(size_t)n * CH + ch];
-                const float z = y * sc + sh, a = z > 0.f ? z : 0.01f * z;
+                const float z = y * sc + sh, a = head_act(z, slope);
                 const float* dd = d.dout + (size_t)n * d.ld_out + d.off[b];
                 float da = 0.f;
 #pragma unroll 4
                 for (int k = 0; k < kb; ++k) { const float dk = dd[k]; da += dk * w[k]; dw[k] += dk * a; }
-                const float gq = da * (z > 0.f ? 1.f : 0.01f);
+                const float gq = da * head_act_grad(z, slope);
                 dsh += gq; dsc += gq * y;
                 if (c < kb) db += dd[c];
                 gy = gq * sc;
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(256) void gram_rows_bwd_kernel(GD d, int rpb, int n
         for (int e = e0; e < e1; ++e) {
             const float y = d.Ye[(size_t)e * GT + c];
             const float z = y * sc + sh;
-            const float gq = (de ? g_ld<T>(de + (size_t)e * GT + c) : 0.f) * (z > 0.f ? 1.f : 0.01f);
+            const float gq = (de ? g_ld<T>(de + (size_t)e * GT + c) : 0.f) * head_act_grad(z, slope);
             dsh += gq; dsc += gq * y;
             g_split<T>(gq * sc, yh, yl, (size_t)e * GT + c);
         }
@@ -499,7 +500,7 @@ template <typename T, int FN, int MODE> static void launch_rowgemm(const RowGemm
     hipLaunchKernelGGL((gram_rowgemm_kernel<T, FN, MODE>), dim3((g.R + 15) / 16, (g.ncols + FN * 64 - 1) / (FN * 64)), dim3(256), 0, st, g);
 }
 
-template <typename T> static int gram_phase(const GD* dp, int phase, hipStream_t st) {
+template <typename T> static int gram_phase(const GD* dp, int phase, float slope, hipStream_t st) {
     const GD& d = *dp;
     const int CH = d.nbranch * GT;
     const int R = d.F + d.N + d.Ne;
@@ -516,7 +517,7 @@ template <typename T> static int gram_phase(const GD* dp, int phase, hipStream_t
             hipLaunchKernelGGL(gram_finalize_kernel, dim3((CH + 255) / 256), dim3(256), 0, st, d);
             RowGemm g = {};
             g.A = reinterpret_cast<const T*>(d.A) + (size_t)d.F * GK; g.Bm = d.Wkc; g.out = d.Y; g.act = d.act; g.sc = d.stat + 3 * CH; g.sh = d.stat + 4 * CH;
-            g.R = d.N; g.K = GK; g.lda = GK; g.ldb = GK; g.ldo = CH; g.ncols = CH; g.act16 = 0;
+            g.R = d.N; g.K = GK; g.lda = GK; g.ldb = GK; g.ldo = CH; g.ncols = CH; g.act16 = 0; g.slope = slope;
             if (d.N > 0) launch_rowgemm<T, 4, 1>(g, st);
             if (d.Ne > 0 && d.extra_branch >= 0) {
                 const int e = d.extra_branch;
@@ -533,7 +534,7 @@ template <typename T> static int gram_phase(const GD* dp, int phase, hipStream_t
             MFX_HIP_CHECK(mfx::zero_async(d.dsum, (size_t)d.arena_bytes, st));
             const int rpb = g_opt_deterministic ? std::max(1, d.N) : 16, nco = d.N > 0 ? (d.N + rpb - 1) / rpb : 0;
             const int rpe = g_opt_deterministic ? std::max(1, d.Ne) : 64, nce = (d.Ne > 0 && d.extra_branch >= 0) ? (d.Ne + rpe - 1) / rpe : 0;
-            if (nco + nce > 0) hipLaunchKernelGGL(gram_rows_bwd_kernel<T>, dim3(nco + nce, d.nbranch), dim3(256), 0, st, d, rpb, nco, rpe);
+            if (nco + nce > 0) hipLaunchKernelGGL(gram_rows_bwd_kernel<T>, dim3(nco + nce, d.nbranch), dim3(256), 0, st, d, rpb, nco, rpe, slope);
             hipLaunchKernelGGL(gram_stats_bwd_kernel, dim3((CH + 255) / 256), dim3(256), 0, st, d);
             break;
         }
@@ -578,15 +579,19 @@ template <typename T> static int gram_phase(const GD* dp, int phase, hipStream_t
 }  // namespace mfx
 using namespace mfx;
 
-extern "C" int mfx_gram_heads(const mfx_gram_desc* d, int phase, void* stream) {
+extern "C" int mfx_gram_heads(const mfx_gram_desc* d, int phase, void* stream) { return mfx_gram_heads_act(d, phase, MFX_ACT_LEAKY, stream); }
+
+extern "C" int mfx_gram_heads_act(const mfx_gram_desc* d, int phase, int act, void* stream) {
     if (!d || !d->x || !d->rows) return mfx_fail(MFX_ERR_ARG, "gram_heads: null pointer");
     if (d->nbranch < 1 || d->nbranch > MFX_HEAD_MAX_BRANCH || d->C != GC) return mfx_fail(MFX_ERR_ARG, "gram_heads: 1..8 branches on a 64-channel map");
     if (d->Ne > 0 && !d->extra_rows) return mfx_fail(MFX_ERR_ARG, "gram_heads: edge rows without their pixel indices");
     for (int b = 0; b < d->nbranch; ++b)
         if (d->k[b] < 1 || d->k[b] > 32 || d->off[b] < 0 || d->off[b] + d->k[b] > d->ld_out) return mfx_fail(MFX_ERR_ARG, "gram_heads: branch outputs out of range");
+    if (act != MFX_ACT_LEAKY && act != MFX_ACT_RELU) return mfx_fail(MFX_ERR_UNSUPPORTED, "gram_heads: the trunk activation is MFX_ACT_LEAKY or MFX_ACT_RELU");
+    const float slope = head_act_slope(act);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (d->dtype == MFX_BF16 || d->dtype == MFX_F16) ++g_cnt_gram;       // one count per phase call
-    if (d->dtype == MFX_BF16) return gram_phase<bf16_t>(d, phase, st);
-    if (d->dtype == MFX_F16) return gram_phase<half_t>(d, phase, st);
+    if (d->dtype == MFX_BF16) return gram_phase<bf16_t>(d, phase, slope, st);
+    if (d->dtype == MFX_F16) return gram_phase<half_t>(d, phase, slope, st);
     return mfx_fail(MFX_ERR_UNSUPPORTED, "gram_heads: 16-bit activations only (fp32 runs the torch form, monoflex_amd/gram_heads.py)");
 }

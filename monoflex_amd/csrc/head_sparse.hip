@@ -5,8 +5,8 @@
 // 50 regression channels at the <= B*MAX_OBJECTS object centres only.  The dense part that cannot be avoided is the trunk
 // convolution and its batch statistics; everything after them is needed at the object pixels alone:
 //
-//   forward   out[n][k] = b2[k] + sum_c W2[k][c] * leaky(y[p_n][c] * scale[c] + shift[c])            (one workgroup per row)
-//   backward  g[n][c]   = leaky'(.) * sum_k dout[n][k] * W2[k][c]   -> Sg, Sgx (BN sums), dW2, db2   (row-chunk workgroups)
+//   forward   out[n][k] = b2[k] + sum_c W2[k][c] * act(y[p_n][c] * scale[c] + shift[c])            (one workgroup per row)
+//   backward  g[n][c]   = act'(.)   * sum_k dout[n][k] * W2[k][c]   -> Sg, Sgx (BN sums), dW2, db2   (row-chunk workgroups)
 //             dx[p][c]  = B[c] * y[p][c] + D[c]  for EVERY pixel (the batch-statistics terms of the BN backward are dense),
 //                         + A[c] * sum_{m: p_m = p} g[m][c] at the object pixels                      (dense pass + fix-up)
 //
@@ -18,6 +18,7 @@
 #include "common.h"
 #include "err.h"
 #include "fill.h"
+#include "head_act.h"
 
 namespace mfx {
 
@@ -26,13 +27,12 @@ enum { HS_VALID = 0, HS_CX = 2, HS_CY = 3, HS_B = 57 };          // object_loss_
 
 struct HsBranch { const void* y; const float* mean; const float* rstd; const float* gamma; const float* beta; const float* w2; const float* b2;
                   float* sums; float* dw2; float* db2; void* dx; int k, off; };
-struct HsGeom { int nbranch, N, B, H, W, ld_out; HsBranch br[MFX_HEAD_MAX_BRANCH]; };
+struct HsGeom { int nbranch, N, B, H, W, ld_out; float slope /* head_act.h */; HsBranch br[MFX_HEAD_MAX_BRANCH]; };
 
 __device__ __forceinline__ long hs_pixel(const float* t, int B, int H, int W) {
     const int b = min(max((int)t[HS_B], 0), B - 1), cx = min(max((int)t[HS_CX], 0), W - 1), cy = min(max((int)t[HS_CY], 0), H - 1);
     return ((long)b * H + cy) * W + cx;
 }
-__device__ __forceinline__ float hs_leaky(float z) { return z > 0.f ? z : 0.01f * z; }
 
 // one workgroup (256 threads = 256 trunk channels) per (object row, branch)
 template <typename T>
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void head_sparse_fwd_kernel(HsGeom g, const fl
     if (t[HS_VALID] == 0.f) { if (c < b.k) o[c] = 0.f; return; }
     const long p = hs_pixel(t, g.B, g.H, g.W);
     const float sc = b.gamma[c] * b.rstd[c], sh = b.beta[c] - b.mean[c] * sc;
-    const float a = hs_leaky(ElemTraits<T>::load(reinterpret_cast<const T*>(b.y) + p * HS_C + c) * sc + sh);
+    const float a = head_act(ElemTraits<T>::load(reinterpret_cast<const T*>(b.y) + p * HS_C + c) * sc + sh, g.slope);
     for (int k = 0; k < b.k; ++k) {
         float v = b.w2[k * HS_C + c] * a;
 #pragma unroll
@@ -74,12 +74,12 @@ __global__ __launch_bounds__(256) void head_sparse_bwd_rows_kernel(HsGeom g, con
         if (t[HS_VALID] != 0.f) {
             const long p = hs_pixel(t, g.B, g.H, g.W);
             const float x = ElemTraits<T>::load(reinterpret_cast<const T*>(b.y) + p * HS_C + c);
-            const float z = x * sc + sh, a = hs_leaky(z);
+            const float z = x * sc + sh, a = head_act(z, g.slope);
             const float* d = dout + (size_t)n * g.ld_out + b.off;
             float da = 0.f;
 #pragma unroll 4
             for (int k = 0; k < b.k; ++k) { const float dk = d[k]; da += dk * w[k]; dw[k] += dk * a; }
-            gq = da * (z > 0.f ? 1.f : 0.01f);
+            gq = da * head_act_grad(z, g.slope);
             sg += gq; sgx += gq * (x - mu) * rs;
             if (c < b.k) db += d[c];
         }
@@ -149,8 +149,10 @@ __global__ __launch_bounds__(256) void head_sparse_fix_kernel(HsGeom g, const fl
     ElemTraits<T>::store(reinterpret_cast<T*>(b.dx) + p * HS_C + c, ca * gs + cb * x + cd);
 }
 
-static int hs_geom(const mfx_head_sparse_desc* d, HsGeom& g, bool backward) {
+static int hs_geom(const mfx_head_sparse_desc* d, int act, HsGeom& g, bool backward) {
     if (!d || !d->rows) return mfx_fail(MFX_ERR_ARG, "head_sparse: null pointer");
+    if (act != MFX_ACT_LEAKY && act != MFX_ACT_RELU) return mfx_fail(MFX_ERR_UNSUPPORTED, "head_sparse: the trunk activation is MFX_ACT_LEAKY or MFX_ACT_RELU");
+    g.slope = head_act_slope(act);
     if (d->nbranch < 1 || d->nbranch > MFX_HEAD_MAX_BRANCH || d->C != HS_C) return mfx_fail(MFX_ERR_ARG, "head_sparse: 1..8 branches of 256 trunk channels");
     if (d->N < 0 || d->B < 1 || d->H < 1 || d->W < 1) return mfx_fail(MFX_ERR_ARG, "head_sparse: bad sizes");
     g.nbranch = d->nbranch; g.N = d->N; g.B = d->B; g.H = d->H; g.W = d->W; g.ld_out = d->ld_out;
@@ -168,9 +170,12 @@ static int hs_geom(const mfx_head_sparse_desc* d, HsGeom& g, bool backward) {
 }  // namespace mfx
 using namespace mfx;
 
-extern "C" int mfx_head_sparse_fwd(const mfx_head_sparse_desc* d, void* stream) {
+extern "C" int mfx_head_sparse_fwd(const mfx_head_sparse_desc* d, void* stream) { return mfx_head_sparse_fwd_act(d, MFX_ACT_LEAKY, stream); }
+extern "C" int mfx_head_sparse_bwd(const mfx_head_sparse_desc* d, void* stream) { return mfx_head_sparse_bwd_act(d, MFX_ACT_LEAKY, stream); }
+
+extern "C" int mfx_head_sparse_fwd_act(const mfx_head_sparse_desc* d, int act, void* stream) {
     HsGeom g;
-    int rc = hs_geom(d, g, false); if (rc) return rc;
+    int rc = hs_geom(d, act, g, false); if (rc) return rc;
     if (!d->out) return mfx_fail(MFX_ERR_ARG, "head_sparse_fwd: null output");
     if (d->N == 0) return MFX_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -182,9 +187,9 @@ extern "C" int mfx_head_sparse_fwd(const mfx_head_sparse_desc* d, void* stream) 
     return MFX_OK;
 }
 
-extern "C" int mfx_head_sparse_bwd(const mfx_head_sparse_desc* d, void* stream) {
+extern "C" int mfx_head_sparse_bwd_act(const mfx_head_sparse_desc* d, int act, void* stream) {
     HsGeom g;
-    int rc = hs_geom(d, g, true); if (rc) return rc;
+    int rc = hs_geom(d, act, g, true); if (rc) return rc;
     if (!d->dout || !d->g || !d->arena || d->arena_bytes == 0) return mfx_fail(MFX_ERR_ARG, "head_sparse_bwd: null pointer");
     if (d->dtype != MFX_F32 && d->dtype != MFX_BF16 && d->dtype != MFX_F16) return mfx_fail(MFX_ERR_ARG, "head_sparse_bwd: bad dtype");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

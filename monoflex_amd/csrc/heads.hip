@@ -108,7 +108,10 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4& hh, u32x4& ll
     }
 }
 
-template <typename T, bool PL, int DBG = 0>
+// ACT: the trunk's activation, a compile-time variant (ACT_LEAKY: InPlaceABN's leaky_relu(0.01); ACT_RELU: BatchNorm2d + ReLU).  The leaky
+// instantiation keeps its instruction sequence (v_pk_fma, v_pk_mul by 0.01, v_max); the ReLU one is v_pk_fma and v_max against +0 -- one
+// instruction fewer per value pair, and +0 (not -0, not -inf) for every z <= 0, which max(z, 0 * z) with a run-time slope of 0 would not give.
+template <typename T, bool PL, int DBG = 0, int ACT = ACT_LEAKY>
 __global__ __launch_bounds__(kHeadWaves * 64, 2) void heads_fused_kernel(const T* __restrict__ x, const u32x4* __restrict__ w1p,
                                                                          const float* __restrict__ scale1, const float* __restrict__ shift1,
                                                                          const u32x4* __restrict__ w2p, const float* __restrict__ bias2,
@@ -312,8 +315,12 @@ __global__ __launch_bounds__(kHeadWaves * 64, 2) void heads_fused_kernel(const T
 #pragma unroll
                 for (int r = 0; r < 4; r += 2) {
                     const f32x2 v = f32x2{acc[i][j][r], acc[i][j][r + 1]} * f32x2{s4[j][r], s4[j][r + 1]} + f32x2{h4[j][r], h4[j][r + 1]};
+                    if constexpr (ACT == ACT_RELU) {
+                        t[j][r] = fmaxf(v[0], 0.f); t[j][r + 1] = fmaxf(v[1], 0.f);
+                    } else {
                     const f32x2 u = v * f32x2{0.01f, 0.01f};
                     t[j][r] = fmaxf(v[0], u[0]); t[j][r + 1] = fmaxf(v[1], u[1]);
+                    }
                 }
             po[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; po[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (SPLIT) {
@@ -394,7 +401,7 @@ template <> __device__ __forceinline__ f32x16 mma32<half_t>(const u32x4& a, cons
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
-template <typename T>
+template <typename T, int ACT = ACT_LEAKY>
 __global__ __launch_bounds__(kHeadWaves * 64, 2) void heads_fused32_kernel(const T* __restrict__ x, const u32x4* __restrict__ w1p, const float* __restrict__ scale1,
                                                                           const float* __restrict__ shift1, const u32x4* __restrict__ w2p,
                                                                           const float* __restrict__ bias2, float* __restrict__ out, HeadGeom g, HeadTabs tabs) {
@@ -531,8 +538,12 @@ __global__ __launch_bounds__(kHeadWaves * 64, 2) void heads_fused32_kernel(const
                     for (int e = 0; e < 8; e += 2) {
                         const int r = 8 * t + e, gq = r >> 2, q = r & 3;
                         const f32x2 v = f32x2{acc[i][j][r], acc[i][j][r + 1]} * f32x2{s4[gq][q], s4[gq][q + 1]} + f32x2{h4[gq][q], h4[gq][q + 1]};
+                        if constexpr (ACT == ACT_RELU) {
+                            v8[e] = fmaxf(v[0], 0.f); v8[e + 1] = fmaxf(v[1], 0.f);
+                        } else {
                         const f32x2 w_ = v * f32x2{0.01f, 0.01f};
                         v8[e] = fmaxf(v[0], w_[0]); v8[e + 1] = fmaxf(v[1], w_[1]);
+                        }
                     }
                     po[i] = mma32<T>(w2f[j][t], ElemTraits<T>::pack(v8), po[i]);
                 }
@@ -583,7 +594,7 @@ __global__ __launch_bounds__(kHeadWaves * 64, 2) void heads_fused32_kernel(const
     }
 }
 
-template <typename T, bool PL, int DBG = 0> static int launch_heads(const mfx_heads_desc* d, hipStream_t st) {
+template <typename T, bool PL, int DBG = 0, int ACT = ACT_LEAKY> static int launch_heads(const mfx_heads_desc* d, hipStream_t st) {
     HeadGeom g;
     g.B = d->B; g.H = d->H; g.W = d->W; g.tiles_x = (d->W + 15) / 16; g.tiles_y = (d->H + kHeadRows - 1) / kHeadRows;
     g.nbranch = d->nbranch; g.ld_out = d->ld_out; g.planar = d->planar; g.planar_c = d->planar_c;
@@ -607,7 +618,7 @@ template <typename T, bool PL, int DBG = 0> static int launch_heads(const mfx_he
     constexpr int smem = HeadSmem<T, PL>::bytes;
     if constexpr (!PL && DBG == 0 && (std::is_same<T, bf16_t>::value || std::is_same<T, half_t>::value)) {
         if (d->w1_32 && d->w2_32 && g_opt_heads_mfma32) {      // the 32x32x16 form (needs its own weight packs)
-            auto k32 = heads_fused32_kernel<T>;
+            auto k32 = heads_fused32_kernel<T, ACT>;
             static bool attr32 = false;
             if (!attr32 && smem > 64 * 1024) { MFX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k32), hipFuncAttributeMaxDynamicSharedMemorySize, smem)); attr32 = true; }
             hipLaunchKernelGGL(k32, dim3(grid), dim3(kHeadWaves * 64), smem, st, reinterpret_cast<const T*>(d->x),
@@ -617,7 +628,7 @@ template <typename T, bool PL, int DBG = 0> static int launch_heads(const mfx_he
             return MFX_OK;
         }
     }
-    auto k = heads_fused_kernel<T, PL, DBG>;
+    auto k = heads_fused_kernel<T, PL, DBG, ACT>;
     static bool attr_set = false;
     if (!attr_set && smem > 64 * 1024) { MFX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, smem)); attr_set = true; }
     hipLaunchKernelGGL(k, dim3(grid), dim3(kHeadWaves * 64), smem, st, reinterpret_cast<const T*>(d->x),
@@ -630,9 +641,20 @@ template <typename T, bool PL, int DBG = 0> static int launch_heads(const mfx_he
 }  // namespace mfx
 using namespace mfx;
 
-extern "C" int mfx_heads_fused(const mfx_heads_desc* d, void* stream) {
+template <int ACT> static int heads_dispatch(const mfx_heads_desc* d, hipStream_t st) {
+    if (d->dtype == MFX_F32) return g_opt_heads_planes ? launch_heads<float, true, 0, ACT>(d, st) : launch_heads<float, false, 0, ACT>(d, st);
+    if (d->dtype == MFX_BF16) return g_opt_heads_planes ? launch_heads<bf16_t, true, 0, ACT>(d, st) : launch_heads<bf16_t, false, 0, ACT>(d, st);
+    if (d->dtype == MFX_F16) return launch_heads<half_t, false, 0, ACT>(d, st);
+    if (d->dtype == MFX_F16X2) return launch_heads<f32s_t, false, 0, ACT>(d, st);
+    return mfx_fail(MFX_ERR_ARG, "heads_fused: bad dtype");
+}
+
+extern "C" int mfx_heads_fused(const mfx_heads_desc* d, void* stream) { return mfx_heads_fused_act(d, MFX_ACT_LEAKY, stream); }
+
+extern "C" int mfx_heads_fused_act(const mfx_heads_desc* d, int act, void* stream) {
     if (!d || !d->x || !d->w1 || !d->scale1 || !d->shift1 || !d->w2 || !d->bias2 || !d->out)
         return mfx_fail(MFX_ERR_ARG, "heads_fused: null pointer");
+    if (act != MFX_ACT_LEAKY && act != MFX_ACT_RELU) return mfx_fail(MFX_ERR_UNSUPPORTED, "heads_fused: the trunk activation is MFX_ACT_LEAKY or MFX_ACT_RELU");
     if (d->nbranch < 1 || d->nbranch > 16) return mfx_fail(MFX_ERR_ARG, "heads_fused: 1..16 branches");
     if (d->K_pad != 9 * kHeadC) return mfx_fail(MFX_ERR_ARG, "heads_fused: K_pad must be 576 (fragment-major packing)");
     for (int i = 0; i < d->nbranch; ++i)
@@ -640,16 +662,13 @@ extern "C" int mfx_heads_fused(const mfx_heads_desc* d, void* stream) {
             return mfx_fail(MFX_ERR_ARG, "heads_fused: branch output channels out of range");
     if (d->B * d->H * d->W == 0) return MFX_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d->dtype == MFX_F32) return g_opt_heads_planes ? launch_heads<float, true>(d, st) : launch_heads<float, false>(d, st);
+    if (act == MFX_ACT_RELU) return heads_dispatch<ACT_RELU>(d, st);
 #ifdef MFX_PROBES      /* timing probes with WRONG results (tools/probes/heads_probe.py): only in a probe build (MFX_PROBES=1 python -m monoflex_amd.build) */
     if (d->dtype == MFX_BF16 && g_opt_heads_dbg == 1) return launch_heads<bf16_t, false, 1>(d, st);
     if (d->dtype == MFX_BF16 && g_opt_heads_dbg == 2) return launch_heads<bf16_t, false, 2>(d, st);
     if (d->dtype == MFX_BF16 && g_opt_heads_dbg == 3) return launch_heads<bf16_t, false, 3>(d, st);
 #endif
-    if (d->dtype == MFX_BF16) return g_opt_heads_planes ? launch_heads<bf16_t, true>(d, st) : launch_heads<bf16_t, false>(d, st);
-    if (d->dtype == MFX_F16) return launch_heads<half_t, false>(d, st);
-    if (d->dtype == MFX_F16X2) return launch_heads<f32s_t, false>(d, st);
-    return mfx_fail(MFX_ERR_ARG, "heads_fused: bad dtype");
+    return heads_dispatch<ACT_LEAKY>(d, st);
 }
 
 MFX_RANGE_FLAG_ACCESSOR(heads)      // split-precision range sentinel of this translation unit (common.h)

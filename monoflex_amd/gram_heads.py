@@ -153,12 +153,22 @@ def _autocorr5(x):
     return dw
 
 
+def _trunk_act(z, act_kind):
+    """The trunk's activation: InPlaceABN's leaky_relu(0.01) (L.ACT_LEAKY) or, with MODEL.INPLACE_ABN False, ReLU (L.ACT_RELU; torch's
+    backward gives the derivative 0 at z == 0, as the kernels do)."""
+    if act_kind == L.ACT_RELU:
+        return F_.relu(z)
+    if act_kind != L.ACT_LEAKY:
+        raise NotImplementedError("gram_reg_heads: the trunk activation is ACT_LEAKY or ACT_RELU, got %r" % (act_kind,))
+    return F_.leaky_relu(z, 0.01)
+
+
 class GramRegHeadsFn(torch.autograd.Function):
     """(x, rows, per-branch trunk weights / ABN gamma, beta / stacked 1x1 weights, biases) -> fp32 [N][ld_out] table of the branches' outputs at
     the object rows (branch i at columns [offs[i], offs[i] + k_i)), as SparseRegHeadsFn returns it -- without the dense trunk maps."""
 
     @staticmethod
-    def forward(ctx, x, rows, abns, offs, ld_out, sync, extra_branch, extra_rows, *ts):
+    def forward(ctx, x, rows, abns, offs, ld_out, sync, act_kind, extra_branch, extra_rows, *ts):
         nb = len(abns)
         ws_, gammas, betas, w2s, b2s = (ts[i * nb:(i + 1) * nb] for i in range(5))
         x = AG._c(x)
@@ -215,7 +225,7 @@ class GramRegHeadsFn(torch.autograd.Function):
             Y_o = A_ol @ Wk.t()
             sc = rstd * gam                                          # BN as one per-channel affine map
             sh = bet - mean * sc
-            act = F_.leaky_relu(_RowAffine.apply(Y_o, sc, sh), 0.01)
+            act = _trunk_act(_RowAffine.apply(Y_o, sc, sh), act_kind)
             # all 1x1 heads as ONE [ld_out x channels] matrix: the branches' weights scattered to their (row block, column block) positions
             w2flat = torch.cat([w.float().reshape(-1) for w in pw2])
             # (torch.full, not torch.zeros: a zero fill of a fresh tensor is a memset node inside a hipGraph capture, and those are not
@@ -230,7 +240,7 @@ class GramRegHeadsFn(torch.autograd.Function):
             if extra_rows is not None:
                 c0 = sum(w.shape[0] for w in pw[:extra_branch]); c1 = c0 + pw[extra_branch].shape[0]
                 Y_e = leaves[4] @ Wk[c0:c1].t()
-                act_e = F_.leaky_relu(_RowAffine.apply(Y_e, sc[c0:c1], sh[c0:c1]), 0.01)
+                act_e = _trunk_act(_RowAffine.apply(Y_e, sc[c0:c1], sh[c0:c1]), act_kind)
         with torch.no_grad():                                         # running statistics: momentum update with the unbiased variance
             unb = var * (float(Mt) / max(Mt - 1, 1))
             c0 = 0
@@ -298,7 +308,7 @@ class GramRegHeadsFn(torch.autograd.Function):
                 dxf.index_add_(0, idx_e.reshape(-1), (grads[4].view(-1, 9, C) * val_e.unsqueeze(-1)).to(dx.dtype).reshape(-1, C))
         it = iter(grads[nl:])
         pg = [next(it) if (p is not None and p.requires_grad) else None for p in params]
-        return (dx, None, None, None, None, None, None, None, *pg)
+        return (dx, None, None, None, None, None, None, None, None, *pg)
 
 
 # ---- the same node as HIP kernels (csrc/gram_heads.hip): 16-bit activations on the GPU; everything else keeps the torch form above ----------
@@ -333,7 +343,7 @@ class GramRegHeadsHipFn(torch.autograd.Function):
     out by hand there.  SyncBN: the two small all-reduces ([sum y | sum y^2] forward, their gradients backward) stay torch.distributed calls."""
 
     @staticmethod
-    def forward(ctx, x, rows, abns, offs, ld_out, sync, extra_branch, extra_rows, *ts):
+    def forward(ctx, x, rows, abns, offs, ld_out, sync, act_kind, extra_branch, extra_rows, *ts):
         nb = len(abns)
         ws_, gammas, betas, w2s, b2s = (ts[i * nb:(i + 1) * nb] for i in range(5))
         x = AG._c(x)
@@ -371,14 +381,14 @@ class GramRegHeadsHipFn(torch.autograd.Function):
         Wkc, WkT = torch.empty((CH, 9 * C), dtype=dt, device=dev), torch.empty((9 * C, CH), dtype=dt, device=dev)
         d.A, d.Wkc, d.WkT = A.data_ptr(), Wkc.data_ptr(), WkT.data_ptr()
         lib_, st = L.load(), ops._stream
-        L.check(lib_.mfx_gram_heads(ctypes.byref(d), 0, st()), "mfx_gram_heads(0)")
+        L.check(lib_.mfx_gram_heads_act(ctypes.byref(d), 0, act_kind, st()), "mfx_gram_heads_act(0)")
         R5, S0 = _autocorr5_rows(x), AG._colsum(x)
         P = _dense_wgrad(A[:F], A[:F], torch.empty((9 * C, 9 * C), **f32))
         csA = AG._colsum(A[:F])
         G, m, Tm = torch.empty((9 * C, 9 * C), **f32), torch.empty(9 * C, **f32), torch.empty((CH, 9 * C), **f32)
         sums, stat = torch.empty(2 * CH, **f32), torch.empty(5 * CH, **f32)
         d.R5, d.S0, d.P, d.csA, d.G, d.m, d.Tm, d.sums, d.stat = (t.data_ptr() for t in (R5, S0, P, csA, G, m, Tm, sums, stat))
-        L.check(lib_.mfx_gram_heads(ctypes.byref(d), 1, st()), "mfx_gram_heads(1)")
+        L.check(lib_.mfx_gram_heads_act(ctypes.byref(d), 1, act_kind, st()), "mfx_gram_heads_act(1)")
         group = AG._sync_group(sync)
         Mt = M
         if group is not None:
@@ -393,8 +403,8 @@ class GramRegHeadsHipFn(torch.autograd.Function):
         covered = sorted((int(o), int(o) + int(w.shape[0])) for o, w in zip(offs, w2c))
         if covered[0][0] != 0 or covered[-1][1] != ld_out or any(a[1] != b[0] for a, b in zip(covered, covered[1:])):
             out.fill_(0.0)                                     # (columns no branch of this call owns: the caller overwrites them)
-        L.check(lib_.mfx_gram_heads(ctypes.byref(d), 2, st()), "mfx_gram_heads(2)")
-        ctx.desc, ctx.group, ctx.geo = d, group, geo
+        L.check(lib_.mfx_gram_heads_act(ctypes.byref(d), 2, act_kind, st()), "mfx_gram_heads_act(2)")
+        ctx.desc, ctx.group, ctx.geo, ctx.act_kind = d, group, geo, act_kind
         ctx.keep = keep + [x, rows, packs, w2c, b2c, A, Wkc, WkT, R5, S0, P, csA, G, m, Tm, sums, stat, Y, act, Ye, act_e, list(gammas), list(betas)]
         ctx.shapes = ([w.shape for w in ws_], [w.shape for w in w2s], [None if b is None else b.shape for b in b2s], nb, Ne, F, CH, N)
         return out, (act_e[:Ne] if Ne else None)
@@ -436,37 +446,38 @@ class GramRegHeadsHipFn(torch.autograd.Function):
             d.db2[i] = db2[i].data_ptr() if db2[i] is not None else None
         d.dYh, d.dYl, d.dYeh, d.dYel, d.dsum, d.ds, d.scal = (t.data_ptr() for t in (dYh, dYl, dYeh, dYel, dsum, ds, scal))
         lib_, st = L.load(), ops._stream
-        L.check(lib_.mfx_gram_heads(ctypes.byref(d), 3, st()), "mfx_gram_heads(3)")
+        L.check(lib_.mfx_gram_heads_act(ctypes.byref(d), 3, ctx.act_kind, st()), "mfx_gram_heads_act(3)")
         if ctx.group is not None:
             import torch.distributed as dist
             dist.all_reduce(ds, group=ctx.group)
         Dw16, dm = torch.empty((CH, 9 * C), dtype=dt, device=dev), torch.empty(9 * C, **f32)
         d.Dw16, d.dm = Dw16.data_ptr(), dm.data_ptr()
-        L.check(lib_.mfx_gram_heads(ctypes.byref(d), 4, st()), "mfx_gram_heads(4)")
+        L.check(lib_.mfx_gram_heads_act(ctypes.byref(d), 4, ctx.act_kind, st()), "mfx_gram_heads_act(4)")
         dGs = _dense_wgrad(Wkc, Dw16, torch.empty((9 * C, 9 * C), **f32))
         Kx, Gn16 = torch.empty((C, C, 5, 5), **f32), torch.empty((9 * C, 9 * C), dtype=dt, device=dev)
         cscale, cshift = torch.empty(C, **f32), torch.empty(C, **f32)
         dAf, dArows = torch.empty((max(F, 1), 9 * C), **f32), torch.empty((max(N + Ne, 1), 9 * C), **f32)
         d.dGs, d.Kx, d.Gn16, d.cscale, d.cshift, d.dAf, d.dArows = (t.data_ptr() for t in (dGs, Kx, Gn16, cscale, cshift, dAf, dArows))
-        L.check(lib_.mfx_gram_heads(ctypes.byref(d), 5, st()), "mfx_gram_heads(5)")
+        L.check(lib_.mfx_gram_heads_act(ctypes.byref(d), 5, ctx.act_kind, st()), "mfx_gram_heads_act(5)")
         p = AG._pack_weight(Kx, dt, 0, C, C, 1, 2, 2)           # one library launch (a temporary: packed now)
         p.scale, p.shift = cscale, cshift
         dx = ops.conv2d(x, p)
         d.dx = dx.data_ptr()
         d.ring_inv, d.ring_idx = geo["inv"].data_ptr(), geo["ring_idx"].data_ptr()
         d.nring, d.ring_width = int(geo["ring_idx"].numel()), int(geo["inv"].shape[1])
-        L.check(lib_.mfx_gram_heads(ctypes.byref(d), 6, st()), "mfx_gram_heads(6)")
+        L.check(lib_.mfx_gram_heads_act(ctypes.byref(d), 6, ctx.act_kind, st()), "mfx_gram_heads_act(6)")
         dwo = _dense_wgrad(A[F:F + N], dYh[:N], torch.empty((CH, 9 * C), **f32)) if N else torch.zeros((CH, 9 * C), **f32)
         dwe = _dense_wgrad(A[F + N:F + N + Ne], dYeh[:Ne], torch.empty((256, 9 * C), **f32)) if Ne else None
         d.dwo, d.dwe = dwo.data_ptr(), (dwe.data_ptr() if dwe is not None else None)
-        L.check(lib_.mfx_gram_heads(ctypes.byref(d), 7, st()), "mfx_gram_heads(7)")
+        L.check(lib_.mfx_gram_heads_act(ctypes.byref(d), 7, ctx.act_kind, st()), "mfx_gram_heads_act(7)")
         ctx.keep = None
         g_w2 = [dw2[i].view(w2shapes[i]) for i in range(nb)]
-        return (dx if ctx.needs_input_grad[0] else None, None, None, None, None, None, None, None, *dwt, *dgam, *dbet, *g_w2, *db2)
+        return (dx if ctx.needs_input_grad[0] else None, None, None, None, None, None, None, None, None, *dwt, *dgam, *dbet, *g_w2, *db2)
 
 
-def gram_reg_heads(x, rows, abns, offs, ld_out, trunk_ws, gammas, betas, w2s, b2s, sync=True, extra_branch=-1, extra_rows=None):
-    """-> (table [N][ld_out], activation rows of branch `extra_branch` at the flat pixel indices `extra_rows` in x's dtype, or None)."""
+def gram_reg_heads(x, rows, abns, offs, ld_out, trunk_ws, gammas, betas, w2s, b2s, sync=True, extra_branch=-1, extra_rows=None, act=L.ACT_LEAKY):
+    """`act`: the trunks' activation, L.ACT_LEAKY (InPlaceABN) or L.ACT_RELU (BatchNorm2d + ReLU).
+    -> (table [N][ld_out], activation rows of branch `extra_branch` at the flat pixel indices `extra_rows` in x's dtype, or None)."""
     def f32c(t):
         return t is not None and t.dtype == torch.float32 and t.is_contiguous()
     # everything the C entry (mfx_gram_heads) requires -- a configuration outside it takes the torch node instead of failing with MFX_ERR_ARG (ADVICE r5):
@@ -478,6 +489,8 @@ def gram_reg_heads(x, rows, abns, offs, ld_out, trunk_ws, gammas, betas, w2s, b2
               and all(f32c(t) for t in list(gammas) + list(betas))
               and all(f32c(a.running_mean) and f32c(a.running_var) for a in abns)
               and len({a.momentum for a in abns}) == 1)
+    if act not in (L.ACT_LEAKY, L.ACT_RELU):
+        raise NotImplementedError("gram_reg_heads: the trunk activation is ACT_LEAKY or ACT_RELU, got %r" % (act,))
     if hip_ok:
-        return GramRegHeadsHipFn.apply(x, rows, tuple(abns), tuple(offs), ld_out, sync, extra_branch, extra_rows, *trunk_ws, *gammas, *betas, *w2s, *b2s)
-    return GramRegHeadsFn.apply(x, rows, tuple(abns), tuple(offs), ld_out, sync, extra_branch, extra_rows, *trunk_ws, *gammas, *betas, *w2s, *b2s)
+        return GramRegHeadsHipFn.apply(x, rows, tuple(abns), tuple(offs), ld_out, sync, act, extra_branch, extra_rows, *trunk_ws, *gammas, *betas, *w2s, *b2s)
+    return GramRegHeadsFn.apply(x, rows, tuple(abns), tuple(offs), ld_out, sync, act, extra_branch, extra_rows, *trunk_ws, *gammas, *betas, *w2s, *b2s)

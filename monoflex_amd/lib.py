@@ -167,9 +167,11 @@ SYMBOLS = {
     "mfx_nhwc_to_nchw": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "mfx_pack_image_nhwc4": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mfx_heads_fused": (_I, [ctypes.POINTER(HeadsDesc), _P]),
+    "mfx_heads_fused_act": (_I, [ctypes.POINTER(HeadsDesc), _I, _P]),
     "mfx_dcn_fuses_offset_conv": (_I, [ctypes.POINTER(DcnDesc)]),
     "mfx_edge_scatter_add": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "mfx_edge_chain": (_I, [ctypes.POINTER(EdgeChainDesc), _P]),
+    "mfx_edge_chain_act": (_I, [ctypes.POINTER(EdgeChainDesc), _I, _P]),
     "mfx_edge_chain_applies": (_I, [ctypes.POINTER(EdgeChainDesc)]),
     "mfx_decode_topk_workspace_bytes": (_S, [_I, _I, _I]),
     "mfx_decode_topk": (_I, [_P, ctypes.c_long, ctypes.c_long, ctypes.c_long, _I, _I, _I, _I, _I, _P, _P, _P, _S, _P]),
@@ -192,6 +194,9 @@ SYMBOLS = {
     "mfx_head_sparse_fwd": (_I, [ctypes.POINTER(HeadSparseDesc), _P]),
     "mfx_head_sparse_bwd": (_I, [ctypes.POINTER(HeadSparseDesc), _P]),
     "mfx_gram_heads": (_I, [ctypes.POINTER(GramDesc), _I, _P]),
+    "mfx_head_sparse_fwd_act": (_I, [ctypes.POINTER(HeadSparseDesc), _I, _P]),
+    "mfx_head_sparse_bwd_act": (_I, [ctypes.POINTER(HeadSparseDesc), _I, _P]),
+    "mfx_gram_heads_act": (_I, [ctypes.POINTER(GramDesc), _I, _I, _P]),
     "mfx_bn_train_stats": (_I, [_P] * 6 + [_F, _F, ctypes.c_long, _I, _I, _P, _P, _P, _I, _P]),
     "mfx_bn_scratch_bytes": (_S, []),
     "mfx_bn_ncopy": (_I, [_I]),

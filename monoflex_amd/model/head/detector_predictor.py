@@ -4,7 +4,9 @@ Parameter names follow the reference (`class_head.{0,1,2}`, `reg_features.{i}.{0
 `reg_heads.{i}.{j}`, `trunc_heatmap_conv.{0,1,3}`, `trunc_offset_conv.{0,1,3}`).  InPlaceABN
 (third-party, not vendored) is held as a plain module with BatchNorm2d's parameter/buffer names;
 its semantics here are BN(eps=1e-5) -> leaky_relu(0.01) (`abn_abs_weight`
-selects upstream's |gamma|+eps variant).
+selects upstream's |gamma|+eps variant).  With MODEL.INPLACE_ABN False (the reference's default) a trunk is
+conv3x3 -> nn.BatchNorm2d -> nn.ReLU, the class head's last layer is `class_head.3`, and the head norms are
+real `_BatchNorm` modules that a SyncBatchNorm conversion reaches; the kernels then apply max(z, 0).
 
 Forward: one fused launch for the nine 3x3->ABN->1x1 branches, then the edge-fusion tail
 (re-evaluates the two needed trunks at the <=832 border points only, Conv1d k3 (replicate pad) +
@@ -70,16 +72,25 @@ class _predictor(nn.Module):
         self.head_conv = cfg.MODEL.HEAD.NUM_CHANNEL
         self.use_inplace_abn = cfg.MODEL.INPLACE_ABN
         self.bn_momentum = cfg.MODEL.HEAD.BN_MOMENTUM
-        self.abn_abs_weight = False
-        if not self.use_inplace_abn or cfg.MODEL.HEAD.USE_NORMALIZATION != "BN":
-            raise NotImplementedError("the HIP heads implement the runs/monoflex.yaml configuration "
-                                      "(INPLACE_ABN True, BN): conv3x3 -> BN -> leaky_relu(0.01) -> conv1x1")
+        self.abn_abs_weight = False                               # (the ABN form only)
+        norm = cfg.MODEL.HEAD.USE_NORMALIZATION
+        if norm == "GN":
+            raise NotImplementedError("MODEL.HEAD.USE_NORMALIZATION 'GN': the reference cannot build these heads either (its group_norm() takes no "
+                                      "'momentum' and raises TypeError); the HIP heads serve 'BN'")
+        if norm != "BN":
+            raise NotImplementedError("MODEL.HEAD.USE_NORMALIZATION %r: heads without a normalisation (the reference's nn.Identity + ReLU trunks) are "
+                                      "not served; the HIP heads fold a BatchNorm into the trunk ('BN')" % (norm,))
+        # the trunk's activation: InPlaceABN's leaky_relu(0.01), or (INPLACE_ABN False) BatchNorm2d -> ReLU
+        self.trunk_act = L.ACT_LEAKY if self.use_inplace_abn else L.ACT_RELU
         if self.head_conv != 256 or in_channels != 64:
             raise NotImplementedError("fused heads kernel is built for 64 -> 256 trunks")
 
         def trunk():
-            return [nn.Conv2d(in_channels, self.head_conv, kernel_size=3, padding=1, bias=False),
-                    InPlaceABN(self.head_conv, momentum=self.bn_momentum, activation="leaky_relu")]
+            conv = nn.Conv2d(in_channels, self.head_conv, kernel_size=3, padding=1, bias=False)
+            if self.use_inplace_abn:
+                return [conv, InPlaceABN(self.head_conv, momentum=self.bn_momentum, activation="leaky_relu")]
+            # parameter holders, as the ABN: the HIP path never calls them
+            return [conv, nn.BatchNorm2d(self.head_conv, momentum=self.bn_momentum), nn.ReLU(inplace=True)]
         self.class_head = nn.Sequential(*trunk(), nn.Conv2d(self.head_conv, classes, kernel_size=1, padding=0, bias=True))
         self.class_head[-1].bias.data.fill_(-np.log(1 / cfg.MODEL.HEAD.INIT_P - 1))
         self.reg_features, self.reg_heads = nn.ModuleList(), nn.ModuleList()
@@ -116,7 +127,7 @@ class _predictor(nn.Module):
 
     # ---- packing ---------------------------------------------------------------------------------
     def _abn_fold(self, abn):
-        if self.abn_abs_weight:                                   # upstream inplace_abn: gamma_eff = |gamma| + eps
+        if self.abn_abs_weight and self.use_inplace_abn:                                  # upstream inplace_abn: gamma_eff = |gamma| + eps
             g = abn.weight.detach().float().abs() + abn.eps
             scale = g / torch.sqrt(abn.running_var.detach().float() + abn.eps)
             return scale, abn.bias.detach().float() - abn.running_mean.detach().float() * scale
@@ -127,20 +138,20 @@ class _predictor(nn.Module):
         if key in self._packs:
             return self._packs[key]
         trunks = [self.class_head] + list(self.reg_features)
-        lasts = [[self.class_head[2]]] + [list(h) for h in self.reg_heads]
+        lasts = [[self.class_head[-1]]] + [list(h) for h in self.reg_heads]
         c_out = [sum(h.weight.shape[0] for h in heads) for heads in lasts]
         ch_off = [0] + [REG_OFF + sum(c_out[1:i]) for i in range(1, len(lasts))]      # the class logits, then the regression branches back to back
         assert ch_off[-1] + c_out[-1] <= HM_LD
         p = ops.pack_heads([t[0].weight for t in trunks], [self._abn_fold(t[1]) for t in trunks],
                            [torch.cat([h.weight for h in heads]) for heads in lasts], [torch.cat([h.bias for h in heads]) for heads in lasts],
-                           self.num_classes, ch_off, HM_LD, dtype)
+                           self.num_classes, ch_off, HM_LD, dtype, act=self.trunk_act)
         # edge fusion: trunks of the class branch and of the 3d_offset branch at the border points
         if self.enable_edge_fusion:
             oi = self.offset_index[0]
             w_e = torch.cat((self.class_head[0].weight, self.reg_features[oi][0].weight), 0)
             s0, b0 = self._abn_fold(self.class_head[1])
             s1, b1 = self._abn_fold(self.reg_features[oi][1])
-            p.edge_trunk = ops.pack_conv(w_e, dtype, torch.cat((s0, s1)), torch.cat((b0, b1)), stride=1, pad=1, act=L.ACT_LEAKY)
+            p.edge_trunk = ops.pack_conv(w_e, dtype, torch.cat((s0, s1)), torch.cat((b0, b1)), stride=1, pad=1, act=self.trunk_act)
             p.edge_branches = []
             for seq, cout, choff in ((self.trunc_heatmap_conv, self.num_classes, 0),
                                      (self.trunc_offset_conv, 2, REG_OFF + sum(sum(c) for c in self.regression_channel_cfg[:oi])
@@ -186,7 +197,7 @@ class _predictor(nn.Module):
 
     def forward_train(self, features, edge_indices=None, edge_lens=None, object_rows=None, plan=None):
         """Training form (detector_predictor.py:125-169), unfused and differentiable: per branch
-        conv3x3 -> ABN(batch statistics, leaky 0.01) -> one 1x1 conv over the branch's stacked heads; edge fusion
+        conv3x3 -> ABN(batch statistics, leaky 0.01; or BN + ReLU) -> one 1x1 conv over the branch's stacked heads; edge fusion
         gathers the two trunks at the border points.  Returns (class logits (B,H,W,ncls), regression (B,H,W,R)).
 
         With `object_rows` (the loss's packed object table, fp32 [N,72]) the regression branches whose activation nothing else
@@ -198,13 +209,16 @@ class _predictor(nn.Module):
         (engine/trainer.prepare_targets) instead of being rebuilt by ~45 tiny launches inside every step."""
         B, H, W, _ = features.shape
         trunks = [self.class_head] + list(self.reg_features)
-        lasts = [[self.class_head[2]]] + [list(h) for h in self.reg_heads]
+        lasts = [[self.class_head[-1]]] + [list(h) for h in self.reg_heads]
         oi = self.offset_index[0]
         sparse = object_rows is not None
         feats, outs, sp = [], [], []
         # the sparse regression branches need no dense trunk map at all when their statistics come from the input's patch Gram matrix
         # (monoflex_amd/gram_heads.py); the class head (dense focal loss) and the 3d_offset head (edge fusion) keep theirs
-        gram = sparse and GRAM_HEADS[0]
+        # (a SYNCHRONISED head norm -- the BN form after a SyncBatchNorm conversion, data parallel -- takes global-batch statistics: the Gram node
+        # and bn_act serve those, SparseRegHeadsFn's statistics are rank-local, so it is not a choice then)
+        synced = any(AG._sync_group(_synced(t[1])) is not None for t in trunks[1:])
+        gram = sparse and (GRAM_HEADS[0] or synced)
         fuse_nodes = self.enable_edge_fusion and self.fused_edge_nodes
         # ... and the 3d_offset branch joins them where the edge fusion reads its trunk through the gathered-rows node: the fusion needs the
         # trunk ACTIVATION at the <= L + 2 edge-sequence pixels of every image, the loss needs the head at the object centres -- both sparse
@@ -228,7 +242,7 @@ class _predictor(nn.Module):
                 sp.append((bi - 1, y, t[1], w, b, done, t[0].weight))
                 feats.append(None); outs.append(None)
                 continue
-            f = AG.bn_act(y, t[1], L.ACT_LEAKY, stats_done=done)
+            f = AG.bn_act(y, t[1], self.trunk_act, stats_done=done)
             feats.append(f)
             if fuse_nodes and (bi == 0 or bi - 1 == oi):
                 # head conv + gather of the trunk's rows at the edge pixels in one node (one data gradient for f)
@@ -302,7 +316,7 @@ class _predictor(nn.Module):
             from monoflex_amd.gram_heads import gram_reg_heads
             tab, _ = gram_reg_heads(features, rows, [e[2] for e in sp], [starts[e[0]] for e in sp], self.reg_width, [e[6] for e in sp],
                                     [e[2].weight for e in sp], [e[2].bias for e in sp], [e[3] for e in sp], [e[4] for e in sp],
-                                    sync=any(bool(getattr(e[2], "sync_bn", False)) for e in sp))
+                                    sync=any(_synced(e[2]) for e in sp), act=self.trunk_act)
         else:
             tab = AG.SparseRegHeadsFn.apply(rows, tuple(e[2] for e in sp), tuple(starts[e[0]] for e in sp), self.reg_width, tuple(e[5] for e in sp),
                                             *[e[1] for e in sp], *[e[2].weight for e in sp], *[e[2].bias for e in sp],
@@ -342,7 +356,7 @@ class _predictor(nn.Module):
         jb = [k for k, e in enumerate(sp) if e[0] == oi]
         return gram_reg_heads(features, rows, [e[2] for e in sp], [starts[e[0]] for e in sp], self.reg_width, [e[6] for e in sp],
                               [e[2].weight for e in sp], [e[2].bias for e in sp], [e[3] for e in sp], [e[4] for e in sp],
-                              sync=any(bool(getattr(e[2], "sync_bn", False)) for e in sp),
+                              sync=any(_synced(e[2]) for e in sp), act=self.trunk_act,
                               extra_branch=jb[0] if (edge_rowmap is not None and jb) else -1, extra_rows=edge_rowmap if jb else None)
 
     def forward(self, features, targets, object_rows=None):
@@ -386,6 +400,11 @@ class _LazyMaps(dict):
 
     def __contains__(self, key):
         return key == 'cls' or super().__contains__(key)
+
+
+def _synced(norm):
+    """Whether a head norm holder was marked (engine.trainer.convert_sync_batchnorm) or replaced (torch's converter) for SyncBN: AG.bn_act's rule."""
+    return bool(getattr(norm, "sync_bn", False)) or isinstance(norm, nn.SyncBatchNorm)
 
 
 def edge_position_of_rows(rows, rows_center, valid_l, B, H, W):

@@ -358,7 +358,7 @@ def heads_fused(x, p: PackedHeads, planar_classes=0):
     for i, (o, c) in enumerate(zip(p.ch_off, p.c_out)):
         d.ch_off[i], d.c_out[i] = o, c
         d.w2_scale[i] = p.w2_scale[i] if p.w2_scale is not None else 1.0
-    L.check(L.load().mfx_heads_fused(ctypes.byref(d), _stream()), "mfx_heads_fused")
+    L.check(L.load().mfx_heads_fused_act(ctypes.byref(d), p.act, _stream()), "mfx_heads_fused_act")
     return out, planar
 
 
@@ -383,7 +383,7 @@ def edge_chain(x, edge_xy, p: PackedEdgeChain):
         return None
     out = torch.empty((2, B, Lmax, 4), dtype=torch.float32, device=x.device)
     d.out = out.data_ptr()
-    L.check(lib.mfx_edge_chain(ctypes.byref(d), _stream()), "mfx_edge_chain")
+    L.check(lib.mfx_edge_chain_act(ctypes.byref(d), p.act_trunk, _stream()), "mfx_edge_chain_act")
     return out
 
 

@@ -7,7 +7,7 @@ from typing import Optional
 
 import torch
 
-from .lib import ACT_NONE, ACT_RELU
+from .lib import ACT_LEAKY, ACT_NONE, ACT_RELU
 
 
 # Compute tag of the split-precision mode (include/monoflex_hip.h MFX_F16X2): activations are ordinary float32 tensors, the GEMM
@@ -157,6 +157,7 @@ class PackedHeads:
     c_out: list
     ld_out: int
     split: bool = False
+    act: int = ACT_LEAKY                     # the trunks' activation (mfx_heads_fused_act): ACT_LEAKY (InPlaceABN) or ACT_RELU (BatchNorm2d + ReLU)
     w2_scale: Optional[list] = None          # per branch, multiplies the 1x1 sums before the bias (split precision: 1 / the weights' packing scale)
     w1_32: Optional[torch.Tensor] = None     # packs of the v_mfma_f32_32x32x16 form of the kernel (16-bit modes; mfx_heads_desc.w1_32 / w2_32)
     w2_32: Optional[torch.Tensor] = None
@@ -177,6 +178,7 @@ class PackedEdgeChain:
     w_out: torch.Tensor         # [2][1][8][4][16][8]
     bias_out: torch.Tensor      # fp32 [2][16]
     relu: bool
+    act_trunk: int = ACT_LEAKY  # the trunk's activation (mfx_edge_chain_act), the row-map trunk pack's
 
 
 def fragment_major(w2d, dtype):
@@ -193,7 +195,7 @@ def pack_edge_chain(trunk: PackedConv, branches):
     pack) as the one-kernel chain reads them: the SAME [rows][K] matrices, K = (tap, channel), fragment-major, so that both forms multiply the
     same numbers in the same K order.  16-bit packs of the 64 -> 256 trunk, a k = 3 Conv1d and at most 4 output channels; None otherwise."""
     dtype = trunk.w.dtype
-    if trunk.split or dtype not in (torch.bfloat16, torch.float16) or len(branches) != 2:
+    if trunk.split or dtype not in (torch.bfloat16, torch.float16) or len(branches) != 2 or trunk.act not in (ACT_LEAKY, ACT_RELU):
         return None
     if (trunk.kh, trunk.kw, trunk.Ck, trunk.Cout, trunk.K_pad) != (3, 3, 64, 512, 576):
         return None
@@ -207,7 +209,7 @@ def pack_edge_chain(trunk: PackedConv, branches):
                            torch.stack([pk1.scale for pk1, _, _, _ in branches]).contiguous(),
                            torch.stack([pk1.shift for pk1, _, _, _ in branches]).contiguous(),
                            torch.stack([fragment_major(pk2.w, dtype) for _, pk2, _, _ in branches]).contiguous(),
-                           torch.stack([pk2.shift for _, pk2, _, _ in branches]).contiguous(), branches[0][0].act == ACT_RELU)
+                           torch.stack([pk2.shift for _, pk2, _, _ in branches]).contiguous(), branches[0][0].act == ACT_RELU, act_trunk=trunk.act)
 
 
 def fold_bn(bn, conv_bias=None):
@@ -351,10 +353,12 @@ def pack_upsample(weight):
     return weight.detach().float().reshape(C, k * k).t().contiguous()
 
 
-def pack_heads(w3x3, folds, w1x1, b1x1, num_classes, ch_off, ld_out, dtype):
+def pack_heads(w3x3, folds, w1x1, b1x1, num_classes, ch_off, ld_out, dtype, act=ACT_LEAKY):
     """The fused heads kernel's operands (csrc/heads.hip).  Per branch (the class head first): `w3x3` the trunk's (256, 64, 3, 3) weight, `folds` its
     folded ABN (scale, shift), `w1x1` / `b1x1` the (c, 256[, 1, 1]) weights and (c,) biases of its stacked 1x1 heads (c <= 32; `num_classes` for the
-    class head), `ch_off` its first channel in the `ld_out`-wide head map; `dtype` the compute tag."""
+    class head), `ch_off` its first channel in the `ld_out`-wide head map; `dtype` the compute tag; `act` the trunks' activation, ACT_LEAKY (the folded ABN's) or ACT_RELU (BatchNorm2d + ReLU)."""
+    if act not in (ACT_LEAKY, ACT_RELU):
+        raise NotImplementedError("pack_heads: the trunk activation is ACT_LEAKY or ACT_RELU, got %r" % (act,))
     nb, hc = len(w3x3), w3x3[0].shape[0]
     w1 = [w.detach().float().permute(0, 2, 3, 1).reshape(hc, -1) for w in w3x3]
     sc, sh = [s for s, _ in folds], [b for _, b in folds]
@@ -393,7 +397,7 @@ def pack_heads(w3x3, folds, w1x1, b1x1, num_classes, ch_off, ld_out, dtype):
             W2 = pair_steps(W2, 2)                              # [branch][wn][kb pair][hi | lo][of][g][o_l][4]
     else:
         W2 = w2.view(nb, 2, 16, 4, 2, 2, 4, 4).permute(0, 3, 4, 1, 6, 2, 5, 7).contiguous().to(dtype)
-    p = PackedHeads(W1, torch.cat(sc).contiguous(), torch.cat(sh).contiguous(), W2, b2.contiguous(), K, list(ch_off), c_out, ld_out, split=dtype == F16X2, w2_scale=w2_scale)
+    p = PackedHeads(W1, torch.cat(sc).contiguous(), torch.cat(sh).contiguous(), W2, b2.contiguous(), K, list(ch_off), c_out, ld_out, split=dtype == F16X2, act=act, w2_scale=w2_scale)
     if dtype in (torch.bfloat16, torch.float16):
         # the same weights for the v_mfma_f32_32x32x16 form (csrc/heads.hip heads_fused32_kernel; option "heads_mfma32"):
         #   3x3: [branch][wn 4][K-step 36][rb 2][h 2][row 32][8], channel 64 wn + 32 rb + row, k = 16 s + 8 h + e

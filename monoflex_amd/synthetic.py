@@ -108,7 +108,7 @@ def synthetic_state_dict(template_state, seed=0, cls_bias=-1.0, offset_std=1.5):
             if ".bn2." in name:                                         # residual branch: keep sums O(1)
                 v = v * 0.4
         elif name.endswith("bias"):
-            if "class_head.2" in name:
+            if "class_head.2" in name or "class_head.3" in name:        # the class head's last layer (.3 with MODEL.INPLACE_ABN False)
                 v = torch.full(shape, float(cls_bias))
             elif "bn" in name or "actf" in name or ".1.bias" in name or "project.1" in name:
                 v = torch.randn(shape, generator=g) * 0.1

@@ -232,7 +232,19 @@ class Checkpointer:
         return torch.load(f, map_location=torch.device("cpu"))
 
     def _load_model(self, ckpt):
-        load_state_dict(self.model, ckpt.pop("model"))
+        loaded = ckpt.pop("model")
+        mapping = load_state_dict(self.model, loaded)
+        # The suffix match keeps a model entry that no checkpoint key serves at its initial value, as the reference does.  Say so: a checkpoint of
+        # the other head form (MODEL.INPLACE_ABN: class_head.2 <-> class_head.3) would otherwise leave the class head's last layer untrained
+        # without a word.  `last_load` keeps the report for the caller.
+        used = set(mapping.values())
+        missing = [k for k in self.model.state_dict() if k not in mapping]
+        unexpected = [k for k in loaded if (k[len("module."):] if k.startswith("module.") else k) not in used and k not in used]
+        self.last_load = dict(mapping=mapping, missing=missing, unexpected=unexpected)
+        if missing:
+            self.logger.warning("checkpoint has no entry for %d model keys (kept as initialised): %s", len(missing), ", ".join(missing[:12]))
+        if unexpected:
+            self.logger.warning("checkpoint entries no model key takes (%d): %s", len(unexpected), ", ".join(unexpected[:12]))
 
 
 class DetectronCheckpointer(Checkpointer):
