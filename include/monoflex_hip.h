@@ -327,7 +327,7 @@ typedef struct {
     const int32_t* edge_xy;        /* [B][L][2] (x, y)                                                               */
     const void* w_trunk;           /* [2 x 256][576] 3x3 trunk weights, the class branch's rows first                 */
     const float* scale_trunk; const float* shift_trunk;   /* [2 x 256] folded ABN                                   */
-    const void* w_conv;            /* [2][256][768] Conv1d weights                                                   */
+    const void* w_conv;            /* [2][256][256 * ksize] Conv1d weights ([2][256][768] for the three entries below) */
     const float* scale_conv; const float* shift_conv;     /* [2][256] folded BN1d (Conv1d bias inside)              */
     const void* w_out;             /* [2][16][256] 1x1 weights, rows past the branch's channels zero                 */
     const float* bias_out;         /* [2][16]                                                                        */
@@ -340,6 +340,13 @@ int mfx_edge_chain(const mfx_edge_chain_desc* d, void* stream);
 int mfx_edge_chain_act(const mfx_edge_chain_desc* d, int act, void* stream);
 /* 1 if mfx_edge_chain takes this configuration and option "edge_chain" is on (the caller then replaces its five conv launches by it) */
 int mfx_edge_chain_applies(const mfx_edge_chain_desc* d);
+/* As mfx_edge_chain_act, for d->ksize in {1, 3, 5, 7} (MODEL.HEAD.EDGE_FUSION_KERNEL_SIZE): the Conv1d reads the trunk rows at positions
+ * p - ksize / 2 .. p + ksize / 2, clamped to 0 .. L-1 (replicate padding), w_conv is [2][256][256 * ksize], K = (tap, channel).  Without a
+ * BatchNorm1d (EDGE_FUSION_NORM not 'BN') the caller passes scale_conv = 1, shift_conv = the Conv1d's bias.  ksize = 3 launches the kernel the
+ * three entries above launch; they keep refusing every other size.  Even sizes, sizes below 1 and above 7: MFX_ERR_UNSUPPORTED.  Counter and
+ * option "edge_chain" cover this entry too.  The descriptor and MFX_ABI_VERSION stay as they are. */
+int mfx_edge_chain_ks(const mfx_edge_chain_desc* d, int act, void* stream);
+int mfx_edge_chain_ks_applies(const mfx_edge_chain_desc* d);
 
 /* Decode stage 1 (layers/utils.py:39-58,61-77): per (image, class) sigmoid+clamp, 3x3 max NMS, top-K.
  * Class logit of (image b, class c, pixel p) is hmap[b*b_stride + c*c_stride + p*p_stride] (elements): either the

@@ -1,13 +1,15 @@
 // The conv chain of the edge fusion (detector_predictor.py:111-119,152-158) as ONE kernel: at the border points of the feature map, per fusion
 // branch (class, 3d_offset)
 //   trunk   3x3 64 -> 256 + folded ABN + LeakyReLU(0.01) (or BN + ReLU: mfx_edge_chain_act)                    (rounded to the activation type)
-//   Conv1d  k = 3 along the point sequence, replicate padded, 256 -> 256 + folded BN1d (+ ReLU)   (rounded to the activation type)
+//   Conv1d  k = KS (1, 3, 5, 7; 3 in runs/monoflex.yaml) along the point sequence, replicate padded, 256 -> 256 + folded BN1d, or the bias alone
+//           where EDGE_FUSION_NORM is not 'BN' (scale = 1, shift = bias) (+ ReLU)                 (rounded to the activation type)
 //   1x1     256 -> c (<= 4) + bias                                                            (fp32)
 // which mfx_conv2d_nhwc runs as five launches (row-map trunk for both branches, then two convs per branch) with the two intermediates in memory.
 //
-// A workgroup owns (a segment of SEG = 62 consecutive sequence positions, a branch, an image): its 64 tile rows are the positions seg * 62 - 1 ..
-// seg * 62 + 62, clamped to 0 .. L - 1 -- the first and the last are the Conv1d's halo, recomputed and never written.  Four waves, each 64 rows x 64
-// channels of the trunk and of the Conv1d (16 accumulator fragments), then one 16-row fragment of the 1x1.  The gathered 3x3 input (64 rows x 9 taps x
+// A workgroup owns (a segment of SEG = 64 - 2 HALO consecutive sequence positions, HALO = KS / 2, a branch, an image): its 64 tile rows are the
+// positions seg * SEG - HALO .. seg * SEG + SEG + HALO - 1, clamped to 0 .. L - 1 (the clamp IS the replicate padding; for L <= HALO several taps
+// read the same position) -- the first and the last HALO are the Conv1d's halo, recomputed and never written (KS = 3: SEG = 62).  Four waves, each 64
+// rows x 64 channels of the trunk and of the Conv1d (16 accumulator fragments), then one 16-row fragment of the 1x1.  The gathered 3x3 input (64 rows x 9 taps x
 // 128 bytes) and the two intermediates live in LDS; the weights stream L2 -> registers through a ring of DEPTH k-steps, fragment-major
 // (packing.fragment_major), so a fragment is one contiguous KiB and a lane's 16 bytes are its MFMA operand.
 //
@@ -20,17 +22,31 @@
 namespace mfx {
 
 namespace ec {
-constexpr int SEG = 62, ROWS = 64;            // positions written per workgroup; tile rows (SEG + the two halo rows)
+constexpr int ROWS = 64;                      // tile rows (the positions written + the halo rows)
 constexpr int CIN = 64, HC = 256;             // feature channels, trunk / Conv1d channels
-constexpr int NK1 = 9 * CIN / 32, NK2 = 3 * HC / 32, NK3 = HC / 32;      // k-steps (32 elements of K) of the three GEMMs: 18, 24, 8
+constexpr int NK1 = 9 * CIN / 32, NK3 = HC / 32;      // k-steps (32 elements of K) of the trunk and of the 1x1: 18, 8
 constexpr int G_ROW = 9 * CIN * 2 + 16;       // bytes of a gathered row (+ one chunk: 16 rows on 16 distinct 16-byte bank slots; 73 slots per row)
 constexpr int T_ROW = HC * 2 + 16;            // bytes of a trunk / Conv1d row (33 slots per row)
 constexpr int G_BYTES = ROWS * G_ROW;         // 74752: the gathered input; the Conv1d output (ROWS * T_ROW) takes its place afterwards
-constexpr int T_BYTES = (ROWS + 2) * T_ROW;   // 34848: trunk rows (two more, never written: tile rows 62 and 63 of the Conv1d read them, nothing keeps their sums)
 constexpr int XY_BYTES = ROWS * 8;
-constexpr int SMEM = G_BYTES + T_BYTES + XY_BYTES;
 constexpr int DEPTH = 6;                      // k-steps of weights in flight per wave (6 x 4 KiB)
 static_assert(ROWS * T_ROW <= G_BYTES, "the Conv1d output reuses the gathered input's space");
+
+// what follows from the Conv1d's window KS (1, 3, 5, 7)
+template <int KS> struct Win {
+    static_assert(KS == 1 || KS == 3 || KS == 5 || KS == 7, "odd windows up to 7");
+    static constexpr int HALO = KS / 2;
+    static constexpr int SEG = ROWS - 2 * HALO;            // positions written per workgroup: 64, 62, 60, 58
+    static constexpr int NK2 = KS * HC / 32;               // k-steps of the Conv1d: 8, 24, 40, 56
+    // trunk rows: KS - 1 more than the tile, never written (Conv1d tile rows SEG .. 63 read them, nothing keeps their sums): 34848 B at KS = 3
+    static constexpr int T_BYTES = (ROWS + KS - 1) * T_ROW;
+    static constexpr int SMEM = G_BYTES + T_BYTES + XY_BYTES;      // 109056, 110112, 111168, 112224
+    static_assert((ROWS - 1) + (NK2 - 1) / 8 < T_BYTES / T_ROW, "the last Conv1d tile row's last k-step reads inside the trunk tile");
+    static_assert(SEG + 2 * HALO == ROWS && SEG > 0, "a segment and its two halos fill the tile");
+    static_assert(T_BYTES % 16 == 0 && SMEM <= 160 * 1024, "the LDS of one CU (one workgroup per CU, as at KS = 3)");
+};
+static_assert(Win<3>::SEG == 62 && Win<3>::NK2 == 24 && Win<3>::SMEM == 110112, "runs/monoflex.yaml's window: the kernel it has always been");
+static_assert(Win<7>::SMEM == 74752 + 70 * 528 + 512, "the largest window");
 }  // namespace ec
 
 struct EdgeChainArgs {
@@ -103,16 +119,17 @@ __device__ __forceinline__ void chain_epilogue(const f32x4 (&acc)[4][4], char* d
 }
 
 // TACT: the trunk's activation (ACT_LEAKY: InPlaceABN; ACT_RELU: BatchNorm2d + ReLU), the expressions of mfx_conv2d_nhwc's epilogue
-template <typename T, int TACT>
+template <typename T, int TACT, int KS>
 __global__ __launch_bounds__(256) void edge_chain_kernel(EdgeChainArgs a) {
     using namespace ec;
+    constexpr int HALO = Win<KS>::HALO, SEG = Win<KS>::SEG, NK2 = Win<KS>::NK2, T_BYTES = Win<KS>::T_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Gs = smem;                          // gathered input, then the Conv1d output
     char* Ts = smem + G_BYTES;                // trunk
     int* xy = reinterpret_cast<int*>(smem + G_BYTES + T_BYTES);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int seg = blockIdx.x, br = blockIdx.y, b = blockIdx.z;
-    const int p0 = seg * SEG;                 // first position written; tile row r is position p0 - 1 + r
+    const int p0 = seg * SEG;                 // first position written; tile row r is position p0 - HALO + r
 
     // weights of the trunk first: they are in flight while the rows are gathered
     u32x4 ring[DEPTH][4];
@@ -120,7 +137,7 @@ __global__ __launch_bounds__(256) void edge_chain_kernel(EdgeChainArgs a) {
     ring_fill<NK1>(ring, w1);
 
     if (tid < ROWS) {
-        const int p = min(max(p0 - 1 + tid, 0), a.L - 1);
+        const int p = min(max(p0 - HALO + tid, 0), a.L - 1);
         const int* e = a.edge_xy + ((size_t)b * a.L + p) * 2;
         xy[2 * tid] = min(max(e[0], 0), a.W - 1);
         xy[2 * tid + 1] = min(max(e[1], 0), a.H - 1);
@@ -158,7 +175,7 @@ __global__ __launch_bounds__(256) void edge_chain_kernel(EdgeChainArgs a) {
     chain_epilogue<T, TACT>(acc, Ts, a.scale_trunk + br * HC, a.shift_trunk + br * HC, wave * 64, lane);
     __syncthreads();                          // trunk complete; every wave is done with the gathered input
 
-    // ---- Conv1d: tile row i = position p0 + i, taps = trunk rows i, i + 1, i + 2; K = (tap, channel)
+    // ---- Conv1d: tile row i = position p0 + i, taps = trunk rows i .. i + KS - 1; K = (tap, channel)
     chain_gemm<T, NK2, T_ROW>(acc, ring, w2, [&](int ks) { return Ts + (frag + (ks >> 3)) * T_ROW + (ks & 7) * 64 + kq16; });
     if (a.relu) chain_epilogue<T, ACT_RELU>(acc, Gs, a.scale_conv + br * HC, a.shift_conv + br * HC, wave * 64, lane);
     else chain_epilogue<T, ACT_NONE>(acc, Gs, a.scale_conv + br * HC, a.shift_conv + br * HC, wave * 64, lane);
@@ -188,15 +205,18 @@ static bool edge_chain_supported(const mfx_edge_chain_desc* d) {
     return (d->dtype == MFX_BF16 || d->dtype == MFX_F16) && d->C == ec::CIN && d->head_conv == ec::HC && d->ksize == 3;
 }
 
-template <typename T, int TACT> static int launch_edge_chain(const EdgeChainArgs& a, hipStream_t st) {
-    auto k = edge_chain_kernel<T, TACT>;
+static bool edge_chain_window_served(int ksize) { return ksize == 1 || ksize == 3 || ksize == 5 || ksize == 7; }
+
+template <typename T, int TACT, int KS = 3> static int launch_edge_chain(const EdgeChainArgs& a, hipStream_t st) {
+    using W = ec::Win<KS>;
+    auto k = edge_chain_kernel<T, TACT, KS>;
     static bool attr_set = false;
     if (!attr_set) {
-        MFX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, ec::SMEM));
+        MFX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, W::SMEM));
         attr_set = true;
     }
-    const int nseg = (a.L + ec::SEG - 1) / ec::SEG;
-    hipLaunchKernelGGL(k, dim3(nseg, 2, a.B), dim3(256), ec::SMEM, st, a);
+    const int nseg = (a.L + W::SEG - 1) / W::SEG;
+    hipLaunchKernelGGL(k, dim3(nseg, 2, a.B), dim3(256), W::SMEM, st, a);
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }
@@ -208,24 +228,53 @@ extern "C" int mfx_edge_chain_applies(const mfx_edge_chain_desc* d) { return (d 
 
 extern "C" int mfx_edge_chain(const mfx_edge_chain_desc* d, void* stream) { return mfx_edge_chain_act(d, MFX_ACT_LEAKY, stream); }
 
-extern "C" int mfx_edge_chain_act(const mfx_edge_chain_desc* d, int act, void* stream) {
+// the argument checks every entry makes before any device work, then the descriptor as kernel arguments; `window_ok`: the entry's own rule for ksize
+static int edge_chain_check(const mfx_edge_chain_desc* d, int act, bool window_ok, const char* window_msg, EdgeChainArgs& a) {
     if (!d || !d->x || !d->edge_xy || !d->w_trunk || !d->scale_trunk || !d->shift_trunk || !d->w_conv || !d->scale_conv || !d->shift_conv ||
         !d->w_out || !d->bias_out || !d->out)
         return mfx_fail(MFX_ERR_ARG, "edge_chain: null pointer");
     if (d->dtype != MFX_BF16 && d->dtype != MFX_F16) return mfx_fail(MFX_ERR_UNSUPPORTED, "edge_chain: bf16 or fp16 activations only");
-    if (!edge_chain_supported(d)) return mfx_fail(MFX_ERR_UNSUPPORTED, "edge_chain: built for 64 feature channels, 256 head channels and a k = 3 Conv1d");
+    if (!window_ok || d->C != ec::CIN || d->head_conv != ec::HC) return mfx_fail(MFX_ERR_UNSUPPORTED, window_msg);
     if (act != MFX_ACT_LEAKY && act != MFX_ACT_RELU) return mfx_fail(MFX_ERR_UNSUPPORTED, "edge_chain: the trunk activation is MFX_ACT_LEAKY or MFX_ACT_RELU");
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->L < 0) return mfx_fail(MFX_ERR_ARG, "edge_chain: bad B / H / W / L");
     if (d->B > 65535) return mfx_fail(MFX_ERR_UNSUPPORTED, "edge_chain: more than 65535 images");
-    if (d->L == 0) return MFX_OK;
-    EdgeChainArgs a;
     a.x = d->x; a.edge_xy = d->edge_xy;
     a.w_trunk = d->w_trunk; a.scale_trunk = d->scale_trunk; a.shift_trunk = d->shift_trunk;
     a.w_conv = d->w_conv; a.scale_conv = d->scale_conv; a.shift_conv = d->shift_conv;
     a.w_out = d->w_out; a.bias_out = d->bias_out; a.out = d->out;
     a.B = d->B; a.H = d->H; a.W = d->W; a.L = d->L; a.relu = d->relu ? 1 : 0;
+    return MFX_OK;
+}
+
+template <int KS> static int launch_edge_chain_ks(const EdgeChainArgs& a, int dtype, int act, hipStream_t st) {
+    if (act == MFX_ACT_RELU) return dtype == MFX_BF16 ? launch_edge_chain<bf16_t, ACT_RELU, KS>(a, st) : launch_edge_chain<half_t, ACT_RELU, KS>(a, st);
+    return dtype == MFX_BF16 ? launch_edge_chain<bf16_t, ACT_LEAKY, KS>(a, st) : launch_edge_chain<half_t, ACT_LEAKY, KS>(a, st);
+}
+
+extern "C" int mfx_edge_chain_act(const mfx_edge_chain_desc* d, int act, void* stream) {
+    EdgeChainArgs a;
+    const int rc = edge_chain_check(d, act, d && d->ksize == 3, "edge_chain: built for 64 feature channels, 256 head channels and a k = 3 Conv1d", a);
+    if (rc != MFX_OK || d->L == 0) return rc;
+    ++g_cnt_edge_chain;
+    return launch_edge_chain_ks<3>(a, d->dtype, act, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mfx_edge_chain_ks_applies(const mfx_edge_chain_desc* d) {
+    return (d && g_opt_edge_chain != 0 && (d->dtype == MFX_BF16 || d->dtype == MFX_F16) && d->C == ec::CIN && d->head_conv == ec::HC &&
+            edge_chain_window_served(d->ksize)) ? 1 : 0;
+}
+
+extern "C" int mfx_edge_chain_ks(const mfx_edge_chain_desc* d, int act, void* stream) {
+    EdgeChainArgs a;
+    const int rc = edge_chain_check(d, act, d && edge_chain_window_served(d->ksize),
+                                    "edge_chain_ks: built for 64 feature channels, 256 head channels and a Conv1d of k = 1, 3, 5 or 7 (odd, at most 7)", a);
+    if (rc != MFX_OK || d->L == 0) return rc;
     ++g_cnt_edge_chain;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (act == MFX_ACT_RELU) return d->dtype == MFX_BF16 ? launch_edge_chain<bf16_t, ACT_RELU>(a, st) : launch_edge_chain<half_t, ACT_RELU>(a, st);
-    return d->dtype == MFX_BF16 ? launch_edge_chain<bf16_t, ACT_LEAKY>(a, st) : launch_edge_chain<half_t, ACT_LEAKY>(a, st);
+    switch (d->ksize) {
+        case 1: return launch_edge_chain_ks<1>(a, d->dtype, act, st);
+        case 3: return launch_edge_chain_ks<3>(a, d->dtype, act, st);      // the instantiation mfx_edge_chain_act launches
+        case 5: return launch_edge_chain_ks<5>(a, d->dtype, act, st);
+        default: return launch_edge_chain_ks<7>(a, d->dtype, act, st);
+    }
 }

@@ -173,6 +173,8 @@ SYMBOLS = {
     "mfx_edge_chain": (_I, [ctypes.POINTER(EdgeChainDesc), _P]),
     "mfx_edge_chain_act": (_I, [ctypes.POINTER(EdgeChainDesc), _I, _P]),
     "mfx_edge_chain_applies": (_I, [ctypes.POINTER(EdgeChainDesc)]),
+    "mfx_edge_chain_ks": (_I, [ctypes.POINTER(EdgeChainDesc), _I, _P]),
+    "mfx_edge_chain_ks_applies": (_I, [ctypes.POINTER(EdgeChainDesc)]),
     "mfx_decode_topk_workspace_bytes": (_S, [_I, _I, _I]),
     "mfx_decode_topk": (_I, [_P, ctypes.c_long, ctypes.c_long, ctypes.c_long, _I, _I, _I, _I, _I, _P, _P, _P, _S, _P]),
     "mfx_conv_wgrad_nhwc": (_I, [_P, _P, _P] + [_I] * 15 + [_P]),

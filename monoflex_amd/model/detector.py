@@ -70,7 +70,7 @@ class KeypointDetector(nn.Module):
         ei, el = stack_edge_fields(targets, device)
         pad, calib, size = self.heads.post_processor.prepare_targets(targets, device)
         pr = self.heads.predictor
-        return ei, el, pad, calib, size, make_edge_rowmap(ei, pr.output_height, pr.output_width)
+        return ei, el, pad, calib, size, make_edge_rowmap(ei, pr.output_height, pr.output_width, pr.edge_halo)
 
     # ---- backward pass in pieces (data-parallel overlap of the gradient exchange; engine/trainer.GraphedTrainStep) -----------------
     BACKWARD_SEGMENTS = 4

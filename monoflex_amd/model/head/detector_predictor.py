@@ -9,8 +9,9 @@ conv3x3 -> nn.BatchNorm2d -> nn.ReLU, the class head's last layer is `class_head
 real `_BatchNorm` modules that a SyncBatchNorm conversion reaches; the kernels then apply max(z, 0).
 
 Forward: one fused launch for the nine 3x3->ABN->1x1 branches, then the edge-fusion tail
-(re-evaluates the two needed trunks at the <=832 border points only, Conv1d k3 (replicate pad) +
-BN1d + Conv1d 1x1, scatter-add into the class / 3d_offset channels).
+(re-evaluates the two needed trunks at the <=832 border points only, Conv1d of MODEL.HEAD.EDGE_FUSION_KERNEL_SIZE
+k = 1, 3, 5 or 7 (replicate pad) + BN1d (EDGE_FUSION_NORM 'BN'; anything else: no norm, the reference's nn.Identity) + optional ReLU + Conv1d 1x1,
+scatter-add into the class / 3d_offset channels).
 """
 import numpy as np
 import torch
@@ -111,17 +112,27 @@ class _predictor(nn.Module):
         self.edge_fusion_kernel_size = cfg.MODEL.HEAD.EDGE_FUSION_KERNEL_SIZE
         self.edge_fusion_relu = cfg.MODEL.HEAD.EDGE_FUSION_RELU
         if self.enable_edge_fusion:
-            if cfg.MODEL.HEAD.EDGE_FUSION_NORM != 'BN' or self.edge_fusion_kernel_size != 3:
-                raise NotImplementedError("edge fusion: k=3 + BN1d configuration only")
+            k = self.edge_fusion_kernel_size
+            if not isinstance(k, int) or k < 1:
+                raise NotImplementedError("MODEL.HEAD.EDGE_FUSION_KERNEL_SIZE %r: the edge fusion's Conv1d window is 1, 3, 5 or 7" % (k,))
+            if k % 2 == 0:
+                raise NotImplementedError("MODEL.HEAD.EDGE_FUSION_KERNEL_SIZE %d: even windows are not served (padding k // 2 on both sides makes the "
+                                          "window asymmetric and the reference's output L + 1 positions long; no released config uses one); "
+                                          "the edge fusion serves 1, 3, 5 and 7" % k)
+            if k > 7:
+                raise NotImplementedError("MODEL.HEAD.EDGE_FUSION_KERNEL_SIZE %d: windows above 7 are not served (mfx_conv2d_nhwc takes kernels up to "
+                                          "8 wide); the edge fusion serves 1, 3, 5 and 7" % k)
+            # 'BN': BatchNorm1d; anything else: no norm, as the reference reads it (its nn.Identity swallows the arguments) -- Conv1d with its bias
+            self.edge_fusion_norm = cfg.MODEL.HEAD.EDGE_FUSION_NORM == 'BN'
             act = nn.ReLU(inplace=True) if self.edge_fusion_relu else nn.Identity()
 
             def trunc(cout):
-                k = self.edge_fusion_kernel_size
                 return nn.Sequential(nn.Conv1d(self.head_conv, self.head_conv, kernel_size=k, padding=k // 2, padding_mode='replicate'),
-                                     nn.BatchNorm1d(self.head_conv, momentum=self.bn_momentum), act,
+                                     nn.BatchNorm1d(self.head_conv, momentum=self.bn_momentum) if self.edge_fusion_norm else nn.Identity(), act,
                                      nn.Conv1d(self.head_conv, cout, kernel_size=1))
             self.trunc_heatmap_conv = trunc(classes)
             self.trunc_offset_conv = trunc(2)
+        self.edge_halo = self.edge_fusion_kernel_size // 2 if self.enable_edge_fusion else 0      # sequence positions the Conv1d reads on either side
         self.num_classes = classes
         self._packs = {}
 
@@ -157,8 +168,8 @@ class _predictor(nn.Module):
                                      (self.trunc_offset_conv, 2, REG_OFF + sum(sum(c) for c in self.regression_channel_cfg[:oi])
                                       + sum(self.regression_channel_cfg[oi][:self.offset_index[1]]))):
                 c1, bn, c3 = seq[0], seq[1], seq[3]
-                scale, shift = ops.fold_bn(bn, c1.bias)
-                # Conv1d weight (256,256,3) -> conv over a 1 x (L+2) "image", taps along W
+                scale, shift = ops.fold_bn(bn, c1.bias)                   # (no norm: scale = 1, shift = the bias; both forms multiply by that 1.0)
+                # Conv1d weight (256,256,k) -> conv over a 1 x (L+k-1) "image", taps along W
                 pk1 = ops.pack_conv(c1.weight.detach().unsqueeze(2), dtype, scale, shift, stride=1, pad=0,
                                     act=L.ACT_RELU if self.edge_fusion_relu else L.ACT_NONE)
                 pk2 = ops.pack_conv(c3.weight.detach().unsqueeze(2), dtype, None, c3.bias, stride=1, pad=0, act=L.ACT_NONE, cout=4)
@@ -186,9 +197,9 @@ class _predictor(nn.Module):
                 for bi, (_, _, cout, choff) in enumerate(p.edge_branches):
                     ops.edge_scatter_add(hm, choff, cout, chain[bi], edge_indices, edge_lens, planar=planar if choff == 0 else None)
                 return hm
-            rowmap = edge_rowmap if edge_rowmap is not None else make_edge_rowmap(edge_indices, H, W)
-            trunk = ops.conv2d(features, p.edge_trunk, rowmap=rowmap)   # (B*(L+2), 512)
-            trunk = trunk.view(B, 1, Lmax + 2, 2 * self.head_conv)
+            rowmap = edge_rowmap if edge_rowmap is not None else make_edge_rowmap(edge_indices, H, W, self.edge_halo)
+            trunk = ops.conv2d(features, p.edge_trunk, rowmap=rowmap)   # (B*(L+k-1), 512)
+            trunk = trunk.view(B, 1, Lmax + 2 * self.edge_halo, 2 * self.head_conv)
             for bi, (pk1, pk2, cout, choff) in enumerate(p.edge_branches):
                 f1 = ops.conv2d(trunk, pk1, x_ch_off=bi * self.head_conv)                  # (B,1,L,256)
                 o = ops.conv2d(f1, pk2, out_dtype=torch.float32)                           # (B,1,L,4) fp32
@@ -221,7 +232,7 @@ class _predictor(nn.Module):
         gram = sparse and (GRAM_HEADS[0] or synced)
         fuse_nodes = self.enable_edge_fusion and self.fused_edge_nodes
         # ... and the 3d_offset branch joins them where the edge fusion reads its trunk through the gathered-rows node: the fusion needs the
-        # trunk ACTIVATION at the <= L + 2 edge-sequence pixels of every image, the loss needs the head at the object centres -- both sparse
+        # trunk ACTIVATION at the <= L + k - 1 edge-sequence pixels of every image, the loss needs the head at the object centres -- both sparse
         gram_off = gram and GRAM_OFFSET[0] and (fuse_nodes or not self.enable_edge_fusion)
         is_sparse = lambda bi: sparse and bi != 0 and (bi - 1 != oi or gram_off)                      # noqa: E731
         dense_ids = [bi for bi in range(len(trunks)) if not (gram and is_sparse(bi))]
@@ -254,11 +265,12 @@ class _predictor(nn.Module):
         cls, regs = outs[0], outs[1:]
         if self.enable_edge_fusion:
             oi, oj = self.offset_index
-            Lmax = edge_indices.shape[1]
+            Lmax, halo = edge_indices.shape[1], self.edge_halo
+            Lpad = Lmax + 2 * halo                                                               # the sequence with its replicate padding
             if not fuse_nodes:
-                pos = torch.arange(-1, Lmax + 1, device=features.device).clamp(0, Lmax - 1)      # replicate padding, k=3
+                pos = torch.arange(-halo, Lmax + halo, device=features.device).clamp(0, Lmax - 1)      # replicate padding
                 xy = edge_indices[:, pos].long()
-                bidx = torch.arange(B, device=features.device).view(B, 1).expand(B, Lmax + 2)
+                bidx = torch.arange(B, device=features.device).view(B, 1).expand(B, Lpad)
             new = []
             gram_tab = None
             if gram_off:
@@ -267,12 +279,15 @@ class _predictor(nn.Module):
                 gram_tab, edge_rows[1 + oi] = self._gram_table(features, object_rows, sp, rowmap if fuse_nodes else None, oi)
             for bi_f, f, seq, base in ((0, feats[0], self.trunc_heatmap_conv, cls), (1 + oi, feats[1 + oi], self.trunc_offset_conv, regs[oi])):
                 if fuse_nodes:
-                    e = edge_rows[bi_f].view(B, 1, Lmax + 2, self.head_conv)
+                    e = edge_rows[bi_f].view(B, 1, Lpad, self.head_conv)
                 else:
-                    e = f[bidx, xy[..., 1], xy[..., 0]].view(B, 1, Lmax + 2, self.head_conv)  # grid_sample at integer points
+                    e = f[bidx, xy[..., 1], xy[..., 0]].view(B, 1, Lpad, self.head_conv)  # grid_sample at integer points
                 c1, bn, c3 = seq[0], seq[1], seq[3]
-                h1 = AG.bn_act(AG.conv2d(e, c1.weight.unsqueeze(2), c1.bias, 1, 0), bn,
-                               L.ACT_RELU if self.edge_fusion_relu else L.ACT_NONE)
+                h1 = AG.conv2d(e, c1.weight.unsqueeze(2), c1.bias, 1, 0)
+                if self.edge_fusion_norm:
+                    h1 = AG.bn_act(h1, bn, L.ACT_RELU if self.edge_fusion_relu else L.ACT_NONE)
+                elif self.edge_fusion_relu:                      # no norm: the Conv1d with its bias, then the ReLU on a (B, 1, L, 256) tensor
+                    h1 = torch.relu(h1)
                 o = AG.conv2d(h1, c3.weight.unsqueeze(2), c3.bias, 1, 0, out_dtype=torch.float32).view(B, Lmax, -1)
                 lo = 0 if base is cls else sum(self.regression_channel_cfg[oi][:oj])
                 co = o.shape[-1]
@@ -328,13 +343,14 @@ class _predictor(nn.Module):
         return cls, torch.cat((tab[:, :lo], off_rows, tab[:, lo + n_off:]), dim=1)
 
     def edge_plan(self, edge_indices, edge_lens, object_rows=None, H=None, W=None):
-        """The edge fusion's index tensors, functions of the targets only (static shapes, no host sync): `rowmap` long [B (L + 2)] pixel rows of
-        the sequence positions -1 .. L (replicate padding, k = 3), `rows_center` [B L] the positions 0 .. L - 1, `valid_l` float [B, L, 1] =
+        """The edge fusion's index tensors, functions of the targets only (static shapes, no host sync): `rowmap` long [B (L + 2 h)] pixel rows of
+        the sequence positions -h .. L - 1 + h (replicate padding, h = k // 2 = `edge_halo`), `rows_center` [B L] the positions 0 .. L - 1, `valid_l` float [B, L, 1] =
         (l < edge_len[b]); with the loss's object table also `e_idx` / `hit` (`edge_plan_rows`)."""
         H, W = H or self.output_height, W or self.output_width
         B, Lm = edge_indices.shape[0], edge_indices.shape[1]
-        rm = make_edge_rowmap(edge_indices, H, W).long()
-        plan = {"rowmap": rm, "rows_center": rm.view(B, Lm + 2)[:, 1:-1].reshape(-1).contiguous(),
+        h = self.edge_halo
+        rm = make_edge_rowmap(edge_indices, H, W, h).long()
+        plan = {"rowmap": rm, "rows_center": rm.view(B, Lm + 2 * h)[:, h:Lm + h].reshape(-1).contiguous(),
                 "valid_l": (torch.arange(Lm, device=rm.device).view(1, Lm) < edge_lens.view(B, 1)).float().unsqueeze(-1)}
         if object_rows is not None:
             plan.update(self.edge_plan_rows(object_rows, plan["rows_center"], plan["valid_l"], B, H, W))
@@ -421,11 +437,11 @@ def edge_position_of_rows(rows, rows_center, valid_l, B, H, W):
     return e_idx, (e_idx >= 0) & (rows[:, 0] > 0)
 
 
-def make_edge_rowmap(edge_indices, H, W):
-    """int32 [B*(L+2)] pixel rows of the edge sequence positions -1..L (replicate padding of the k=3 Conv1d,
-    detector_predictor.py:111-119).  Depends on the targets only: computed once per batch, not per forward."""
+def make_edge_rowmap(edge_indices, H, W, halo=1):
+    """int32 [B*(L+2*halo)] pixel rows of the edge sequence positions -halo .. L-1+halo, clamped to 0 .. L-1 (replicate padding of the Conv1d of
+    window k = 2 halo + 1, detector_predictor.py:111-119; halo = 1: k = 3).  Depends on the targets only: computed once per batch, not per forward."""
     B, Lmax = edge_indices.shape[0], edge_indices.shape[1]
-    pos = torch.arange(-1, Lmax + 1, device=edge_indices.device).clamp(0, Lmax - 1)
+    pos = torch.arange(-halo, Lmax + halo, device=edge_indices.device).clamp(0, Lmax - 1)
     xy = edge_indices[:, pos].long()
     rm = torch.arange(B, device=edge_indices.device).view(B, 1) * (H * W) + xy[..., 1] * W + xy[..., 0]
     return rm.to(torch.int32).reshape(-1).contiguous()

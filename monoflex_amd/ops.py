@@ -366,7 +366,8 @@ def heads_fused(x, p: PackedHeads, planar_classes=0):
 def edge_chain(x, edge_xy, p: PackedEdgeChain):
     """The edge fusion's conv chain in one kernel: x (B,H,W,64) 16-bit, edge_xy int32 (B,L,2) -> fp32 (2,B,L,4), [0] the class branch's and [1]
     the 3d_offset branch's Conv1d output at every sequence position (what edge_scatter_add adds to the head map).  None where the library keeps
-    the five conv launches (option "edge_chain" off, or not a 16-bit map): the caller runs those."""
+    the five conv launches (option "edge_chain" off, or not a 16-bit map): the caller runs those.  A k = 3 pack goes through mfx_edge_chain_applies /
+    mfx_edge_chain_act, the other windows (p.ksize 1, 5, 7) through mfx_edge_chain_ks_applies / mfx_edge_chain_ks."""
     _need_cuda(x, edge_xy)
     B, H, W, C = x.shape
     Lmax = edge_xy.shape[1]
@@ -377,13 +378,15 @@ def edge_chain(x, edge_xy, p: PackedEdgeChain):
     d.w_trunk, d.scale_trunk, d.shift_trunk = p.w_trunk.data_ptr(), p.scale_trunk.data_ptr(), p.shift_trunk.data_ptr()
     d.w_conv, d.scale_conv, d.shift_conv = p.w_conv.data_ptr(), p.scale_conv.data_ptr(), p.shift_conv.data_ptr()
     d.w_out, d.bias_out = p.w_out.data_ptr(), p.bias_out.data_ptr()
-    d.B, d.H, d.W, d.C, d.L, d.head_conv, d.ksize, d.relu, d.dtype = B, H, W, C, Lmax, 256, 3, int(p.relu), _dt(x.dtype)
+    d.B, d.H, d.W, d.C, d.L, d.head_conv, d.ksize, d.relu, d.dtype = B, H, W, C, Lmax, 256, p.ksize, int(p.relu), _dt(x.dtype)
     lib = L.load()
-    if not lib.mfx_edge_chain_applies(ctypes.byref(d)):
+    applies, run, name = (lib.mfx_edge_chain_applies, lib.mfx_edge_chain_act, "mfx_edge_chain_act") if p.ksize == 3 else \
+        (lib.mfx_edge_chain_ks_applies, lib.mfx_edge_chain_ks, "mfx_edge_chain_ks")
+    if not applies(ctypes.byref(d)):
         return None
     out = torch.empty((2, B, Lmax, 4), dtype=torch.float32, device=x.device)
     d.out = out.data_ptr()
-    L.check(lib.mfx_edge_chain_act(ctypes.byref(d), p.act_trunk, _stream()), "mfx_edge_chain_act")
+    L.check(run(ctypes.byref(d), p.act_trunk, _stream()), name)
     return out
 
 

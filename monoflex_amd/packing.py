@@ -162,23 +162,27 @@ class PackedHeads:
     w1_32: Optional[torch.Tensor] = None     # packs of the v_mfma_f32_32x32x16 form of the kernel (16-bit modes; mfx_heads_desc.w1_32 / w2_32)
     w2_32: Optional[torch.Tensor] = None
     edge_trunk: Optional[PackedConv] = None  # edge fusion (detector_predictor._pack): the class and 3d_offset trunks as one conv at the border points
-    edge_branches: Optional[list] = None     # ... and per fusion branch (Conv1d k3 pack, Conv1d 1x1 pack, channels, channel offset in the head map)
+    edge_branches: Optional[list] = None     # ... and per fusion branch (Conv1d pack (k = 1, 3, 5, 7), Conv1d 1x1 pack, channels, channel offset in the head map)
     edge_chain: Optional["PackedEdgeChain"] = None   # the same five operands for the one-kernel chain (16-bit modes; pack_edge_chain)
 
 
 @dataclass
 class PackedEdgeChain:
-    """mfx_edge_chain's operands (csrc/edge_chain.hip): fragment-major weights, branch 0 = class, 1 = 3d_offset."""
+    """mfx_edge_chain's / mfx_edge_chain_ks's operands (csrc/edge_chain.hip): fragment-major weights, branch 0 = class, 1 = 3d_offset."""
     w_trunk: torch.Tensor       # [2 x 16][18][4][16][8]
     scale_trunk: torch.Tensor   # fp32 [2 x 256]
     shift_trunk: torch.Tensor
-    w_conv: torch.Tensor        # [2][16][24][4][16][8]
-    scale_conv: torch.Tensor    # fp32 [2][256]
+    w_conv: torch.Tensor        # [2][16][8 ksize][4][16][8]
+    scale_conv: torch.Tensor    # fp32 [2][256] (no BatchNorm1d: ones, and shift_conv the Conv1d's bias)
     shift_conv: torch.Tensor
     w_out: torch.Tensor         # [2][1][8][4][16][8]
     bias_out: torch.Tensor      # fp32 [2][16]
     relu: bool
     act_trunk: int = ACT_LEAKY  # the trunk's activation (mfx_edge_chain_act), the row-map trunk pack's
+    ksize: int = 3              # the Conv1d's window (MODEL.HEAD.EDGE_FUSION_KERNEL_SIZE): 1, 3, 5 or 7
+
+
+EDGE_CHAIN_KSIZES = (1, 3, 5, 7)    # the windows csrc/edge_chain.hip is instantiated for
 
 
 def fragment_major(w2d, dtype):
@@ -191,16 +195,19 @@ def fragment_major(w2d, dtype):
 
 
 def pack_edge_chain(trunk: PackedConv, branches):
-    """The edge fusion's five conv operands (detector_predictor._pack: the row-map trunk of both branches, per branch the Conv1d k3 and the 1x1
+    """The edge fusion's five conv operands (detector_predictor._pack: the row-map trunk of both branches, per branch the Conv1d and the 1x1
     pack) as the one-kernel chain reads them: the SAME [rows][K] matrices, K = (tap, channel), fragment-major, so that both forms multiply the
-    same numbers in the same K order.  16-bit packs of the 64 -> 256 trunk, a k = 3 Conv1d and at most 4 output channels; None otherwise."""
+    same numbers in the same K order.  16-bit packs of the 64 -> 256 trunk, a Conv1d of k = 1, 3, 5 or 7 and at most 4 output channels; None otherwise."""
     dtype = trunk.w.dtype
     if trunk.split or dtype not in (torch.bfloat16, torch.float16) or len(branches) != 2 or trunk.act not in (ACT_LEAKY, ACT_RELU):
         return None
     if (trunk.kh, trunk.kw, trunk.Ck, trunk.Cout, trunk.K_pad) != (3, 3, 64, 512, 576):
         return None
+    k = branches[0][0].kw
+    if k not in EDGE_CHAIN_KSIZES:
+        return None
     for pk1, pk2, cout, _ in branches:
-        if (pk1.kh, pk1.kw, pk1.Ck, pk1.Cout, pk1.K_pad) != (1, 3, 256, 256, 768) or pk1.act not in (ACT_NONE, ACT_RELU) or pk1.act != branches[0][0].act:
+        if (pk1.kh, pk1.kw, pk1.Ck, pk1.Cout, pk1.K_pad) != (1, k, 256, 256, 256 * k) or pk1.act not in (ACT_NONE, ACT_RELU) or pk1.act != branches[0][0].act:
             return None
         if (pk2.kh, pk2.kw, pk2.Ck, pk2.Cout_pad, pk2.K_pad) != (1, 1, 256, 16, 256) or cout > 4 or pk2.scale is not None or pk2.act != ACT_NONE:
             return None
@@ -209,11 +216,17 @@ def pack_edge_chain(trunk: PackedConv, branches):
                            torch.stack([pk1.scale for pk1, _, _, _ in branches]).contiguous(),
                            torch.stack([pk1.shift for pk1, _, _, _ in branches]).contiguous(),
                            torch.stack([fragment_major(pk2.w, dtype) for _, pk2, _, _ in branches]).contiguous(),
-                           torch.stack([pk2.shift for _, pk2, _, _ in branches]).contiguous(), branches[0][0].act == ACT_RELU, act_trunk=trunk.act)
+                           torch.stack([pk2.shift for _, pk2, _, _ in branches]).contiguous(), branches[0][0].act == ACT_RELU, act_trunk=trunk.act, ksize=k)
 
 
 def fold_bn(bn, conv_bias=None):
-    """Eval-mode BatchNorm as y = x*scale + shift (a preceding conv bias folded in)."""
+    """Eval-mode BatchNorm as y = x*scale + shift (a preceding conv bias folded in).  No norm (`bn` None or an nn.Identity, the reference's
+    stand-in where a norm setting is not 'BN'): scale = 1, shift = the bias -- the kernels' acc * 1 + bias is exact."""
+    if bn is None or isinstance(bn, torch.nn.Identity):
+        if conv_bias is None:
+            raise ValueError("fold_bn: neither a norm nor a bias")
+        shift = conv_bias.detach().float()
+        return torch.ones_like(shift).contiguous(), shift.contiguous()
     scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
     shift = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
     if conv_bias is not None:
