@@ -81,7 +81,8 @@ int mfx_commit_options(void);
  *   BN: "bn_fwd_onepass" / "bn_bwd_onepass" (one-launch grid-barrier kernels), "bn_fwd_two" / "bn_bwd_two" (mfx_bn_train_fwd / _bwd calls
  *   that took the two-launch form), "conv_bn_stats" (convs whose epilogue accumulated the following BN's statistics);
  *   DCN backward: "dcn_bt_tile" (dcn_bwd_tile_kernel), "dcn_bt_sample" (dcn_bwd_sample_kernel), "dcn_bt_far" (far-corner kernels, both forms);
- *   "gram" (mfx_gram_heads phase calls), "adamw_multi" (one-launch AdamW).
+ *   "gram" (mfx_gram_heads phase calls), "adamw_multi" (one-launch AdamW), "optim_multi" (mfx_optim_multi: the one-launch update with a rule
+ *   and / or a gradient coefficient), "grad_norm_multi" (mfx_grad_norm_multi: the gradient norm of the clipped update).
  * Unknown names return MFX_ERR_ARG (negative). */
 long mfx_get_counter(const char* name);
 
@@ -485,6 +486,24 @@ typedef struct mfx_adamw_group {
 int mfx_adamw_chunk_elems(void);
 int mfx_adamw_multi(const mfx_adamw_desc* descs_dev, const long long* prefix_dev, int n, long long total_chunks,
                     const mfx_adamw_group* groups_dev, const float* found_inf, void* stream);
+/* The same launch with a choice of update rule and an optional gradient coefficient (SOLVER.OPTIMIZER 'adam', SOLVER.GRAD_NORM_CLIP):
+ *   rule       MFX_OPTIM_ADAMW (0): the arithmetic of mfx_adamw_multi.  MFX_OPTIM_ADAM_L2 (1): torch.optim.Adam with L2 weight decay (reference
+ *              solver/__init__.py:33-34; torch's capturable `_fused_adam_`): g' = g + weight_decay p, both moments on g', then the same bias-corrected step.
+ *   grad_coef  device fp32 scalar or NULL: every gradient element is multiplied by it in fp32 before anything else (the rounding of scaling the
+ *              gradient in place and reading it back).  The gradient tensors are NOT written: after a clipped step they keep the unclipped values.
+ * Step counters, `found_inf` and unaligned storage as in mfx_adamw_multi; mfx_adamw_multi is this entry with (MFX_OPTIM_ADAMW, NULL), its own counter kept. */
+#define MFX_OPTIM_ADAMW 0
+#define MFX_OPTIM_ADAM_L2 1
+int mfx_optim_multi(const mfx_adamw_desc* descs_dev, const long long* prefix_dev, int n, long long total_chunks,
+                    const mfx_adamw_group* groups_dev, int rule, const float* grad_coef, const float* found_inf, void* stream);
+/* Gradient-norm clipping of that update (reference engine/trainer.py:119 torch.nn.utils.clip_grad_norm_, norm type 2) over the same tables:
+ * one workgroup per chunk sums the squares of its gradient elements in fp32 (16 per thread in series, then a fixed tree) and stores one partial
+ * in `workspace` (mfx_grad_norm_workspace_bytes(total_chunks) bytes); one workgroup then adds the partials in a fixed order in double and writes
+ *   out2[0] = total_norm,  out2[1] = coef = min(1, max_norm / (total_norm + 1e-6))      (fp32 device scalars; hand out2 + 1 to mfx_optim_multi)
+ * No atomics: the result is the same bits in every run and on every rank that holds the same gradients.  A set `found_inf` leaves coef at 1. */
+size_t mfx_grad_norm_workspace_bytes(long long total_chunks);
+int mfx_grad_norm_multi(const mfx_adamw_desc* descs_dev, const long long* prefix_dev, int n, long long total_chunks, float max_norm,
+                        void* workspace, size_t workspace_bytes, float* out2, const float* found_inf, void* stream);
 /* out[c] = sum_m x[m*ld + c]  (bias gradients) */
 int mfx_colsum(const void* x, float* out, long M, int C, int ld, int dtype, void* stream);
 /* out[c] += sum_m x[m*ld + c]: the same without the zero fill (a caller that carves many `out` vectors from one arena zeroes the arena once) */
@@ -600,7 +619,15 @@ int mfx_focal_loss(const float* logits_nhwc, const float* heat_nchw, int B, int 
  * logged values are 0, the rest follows the reference's branches for the missing head: plain L1 depth, three-way combination of the keypoint
  * depths, keypoint depths without exp(-u)).  MFX_ERR_ARG: a required key absent, a key reaching past reg_width, corner_uncertainty without
  * corner_offset, a corner_depth_mode the set cannot serve (keypoint_mean needs corner_offset; soft / hard combine need all nine keys).
- * mfx_object_loss_backward is mfx_object_loss_backward_width with reg_width = 50; only channels [ch_off, ch_off + reg_width) are written. */
+ * mfx_object_loss_backward is mfx_object_loss_backward_width with reg_width = 50; only channels [ch_off, ch_off + reg_width) are written.
+ * Loss types (MODEL.HEAD.LOSS_TYPE entries 1 and 3, detector_loss.py:45-53): mfx_object_loss_types takes the two kinds beside the configuration --
+ * mfx_object_loss_cfg and MFX_ABI_VERSION stay as they are; mfx_object_loss is this entry with (0, 0).
+ *   reg_loss    0 'L1', 1 smooth L1 (beta 1; any other string of the reference): the offset coordinates (summed before the log of the truncated
+ *               term), the dimensions (before DIMENSION_WEIGHT), the corner coordinates, the keypoint depths (before exp(-u)), the combined depth.
+ *               Keypoints, multi-bin residuals and the direct depth do not take it.
+ *   depth_loss  0 'L1', 1 'log' |log p - log t| on the decoded, clamped depth, 2 'inv_sig' as the reference computes it: |1/sigmoid(t) - 1 - t|,
+ *               a function of the target alone (zero gradient for the depth channel; the depth uncertainty keeps its own).
+ * The logged depth_loss / keypoint_depth_loss follow the kinds, the MAEs do not.  A kind out of range: MFX_ERR_ARG.  The backward entries consume G. */
 #define MFX_OBJ_ROW 72
 #define MFX_OBJ_TERMS 10
 #define MFX_OBJ_VALUES 24
@@ -620,6 +647,8 @@ typedef struct mfx_object_loss_cfg {
 } mfx_object_loss_cfg;
 int mfx_object_loss(const float* reg_nhwc, int B, int H, int W, int ld, int ch_off, const float* rows, int N,
                     const mfx_object_loss_cfg* cfg, float* vals, float* G, void* stream);
+int mfx_object_loss_types(const float* reg_nhwc, int B, int H, int W, int ld, int ch_off, const float* rows, int N,
+                          const mfx_object_loss_cfg* cfg, int reg_loss, int depth_loss, float* vals, float* G, void* stream);
 int mfx_object_loss_backward(const float* G, const float* gout_terms, const float* rows, int N, int B, int H, int W,
                              float* dreg_nhwc, int ld, int ch_off, void* stream);
 int mfx_object_loss_backward_width(const float* G, const float* gout_terms, const float* rows, int N, int B, int H, int W,

@@ -1073,10 +1073,13 @@ class ObjectLossFn(Function):
     """The nine per-object regression terms (detector_loss.py:116-482) in one launch (csrc/object_loss_math.h): fp32 NHWC map
     with the R = cfg.reg_width (0: 50) regression channels at [ch_off, ch_off+R) of each pixel + the packed target rows -> (terms[10], logged[14]);
     the gradient row of every term is produced by the same launch (forward-mode tangents, one lane per channel), backward is a
-    scatter-add of sum_t gout[t] * G[n][t][:] into a zero map."""
+    scatter-add of sum_t gout[t] * G[n][t][:] into a zero map.  `reg_loss` / `depth_loss`: the loss kinds of MODEL.HEAD.LOSS_TYPE entries 1 and 3
+    (lib.REG_LOSSES / lib.DEPTH_LOSSES indices; mfx_object_loss_types), in both addressing forms; (0, 0) = L1 + L1 is mfx_object_loss."""
 
     @staticmethod
-    def forward(ctx, reg_nhwc, rows, cfg, ch_off):
+    def forward(ctx, reg_nhwc, rows, cfg, ch_off, *kinds):
+        reg_loss, depth_loss = kinds if kinds else (getattr(cfg, "reg_loss", 0), getattr(cfg, "depth_loss", 0))      # (Loss_Computation.object_loss_cfg carries them)
+        ctx.nkinds = len(kinds)
         reg = _c(reg_nhwc)
         if reg.dtype != torch.float32 or rows.dtype != torch.float32:
             raise TypeError("object loss: fp32 regression map and fp32 target rows")
@@ -1090,8 +1093,8 @@ class ObjectLossFn(Function):
         N = rows.shape[0]
         vals = torch.empty(L.OBJ_VALUES, dtype=torch.float32, device=reg.device)
         G = torch.empty(N, L.OBJ_TERMS, 64, dtype=torch.float32, device=reg.device)
-        L.check(L.load().mfx_object_loss(_ptr(reg), B, H, W, ld, ch_off, _ptr(rows), N, ctypes.byref(cfg), _ptr(vals), _ptr(G), _stream()),
-                "mfx_object_loss")
+        L.check(L.load().mfx_object_loss_types(_ptr(reg), B, H, W, ld, ch_off, _ptr(rows), N, ctypes.byref(cfg), int(reg_loss), int(depth_loss),
+                                               _ptr(vals), _ptr(G), _stream()), "mfx_object_loss_types")
         ctx.save_for_backward(G, rows)
         ctx.geom = (B, H, W, ld, ch_off, cfg.reg_width or 50)
         terms, logged = vals[:L.OBJ_TERMS], vals[L.OBJ_TERMS:]
@@ -1107,7 +1110,7 @@ class ObjectLossFn(Function):
         g = _c(g_terms.float())
         L.check(L.load().mfx_object_loss_backward_width(_ptr(G), _ptr(g), _ptr(rows), rows.shape[0], B, H, W, _ptr(dreg), ld, ch_off, R, _stream()),
                 "mfx_object_loss_backward_width")
-        return dreg, None, None, None
+        return (dreg, None, None, None) + (None,) * ctx.nkinds
 
 
 def trunk_act(norm):

@@ -90,6 +90,8 @@ __device__ __forceinline__ const float* object_pixel(const float* base, const fl
     return base + ((size_t)(b * H + cy) * W + cx) * ld + ch_off;
 }
 
+// <REG, DEP>: the two loss kinds of MODEL.HEAD.LOSS_TYPE (object_loss_math.h reg_loss / depth_loss); <0, 0> is L1 + L1
+template <int REG, int DEP>
 __global__ __launch_bounds__(64) void object_loss_kernel(const float* __restrict__ reg, int B, int H, int W, int ld, int ch_off,
                                                          const float* __restrict__ rows, int N, mfx_object_loss_cfg c,
                                                          float* __restrict__ vals, float* __restrict__ G) {
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(64) void object_loss_kernel(const float* __restrict
         const float* t = rows + (size_t)n * ROW;
         Dual out[NVAL];
         const PixelReader X{object_pixel(reg, t, n, B, H, W, ld, ch_off), lane};
-        object_terms(X, t, c, cn, out);
+        object_terms_t<REG, DEP>(X, t, c, cn, out);
 #pragma unroll
         for (int k = 0; k < NTERM; ++k) G[((size_t)n * NTERM + k) * 64 + lane] = out[k].d;
         if (lane == 0 && t[R_VALID] != 0.f)
@@ -139,6 +141,12 @@ __global__ __launch_bounds__(64) void object_loss_bwd_kernel(const float* __rest
 
 extern "C" int mfx_object_loss(const float* reg_nhwc, int B, int H, int W, int ld, int ch_off, const float* rows, int N,
                                const mfx_object_loss_cfg* cfg, float* vals, float* G, void* stream) {
+    return mfx_object_loss_types(reg_nhwc, B, H, W, ld, ch_off, rows, N, cfg, REG_L1, DEP_L1, vals, G, stream);
+}
+
+extern "C" int mfx_object_loss_types(const float* reg_nhwc, int B, int H, int W, int ld, int ch_off, const float* rows, int N,
+                                     const mfx_object_loss_cfg* cfg, int reg_loss, int depth_loss, float* vals, float* G, void* stream) {
+    if (!loss_kinds_ok(reg_loss, depth_loss)) return mfx_fail(MFX_ERR_ARG, "object_loss: reg_loss must be 0 (L1) or 1 (smooth L1), depth_loss 0 (L1), 1 (log) or 2 (inv_sig)");
     if (!reg_nhwc || !rows || !cfg || !vals || !G) return mfx_fail(MFX_ERR_ARG, "object_loss: null pointer");
     if (cfg->reg_width < 0 || cfg->reg_width > MAX_REG) return mfx_fail(MFX_ERR_ARG, "object_loss: reg_width must be 0 (the full 50) or 1..50");
     if (B < 0 || (B > 0 && (H < 1 || W < 1)) || N < 0 || ch_off < 0 || ch_off + reg_width(*cfg) > ld) return mfx_fail(MFX_ERR_ARG, "object_loss: bad sizes");
@@ -146,7 +154,11 @@ extern "C" int mfx_object_loss(const float* reg_nhwc, int B, int H, int W, int l
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MFX_HIP_CHECK(mfx::zero_async(vals, sizeof(float) * MFX_OBJ_VALUES, st));
     if (N == 0) return MFX_OK;
-    hipLaunchKernelGGL(object_loss_kernel, dim3(g_opt_deterministic ? 1 : N), dim3(64), 0, st, reg_nhwc, B, H, W, ld, ch_off, rows, N, *cfg, vals, G);
+    // (option "deterministic": ONE wave walks the objects in order, whichever kinds)
+#define MFX_OBJECT_LOSS_LAUNCH(R_, D_) \
+    hipLaunchKernelGGL((object_loss_kernel<R_, D_>), dim3(g_opt_deterministic ? 1 : N), dim3(64), 0, st, reg_nhwc, B, H, W, ld, ch_off, rows, N, *cfg, vals, G)
+    MFX_LOSS_KINDS(reg_loss, depth_loss, MFX_OBJECT_LOSS_LAUNCH)
+#undef MFX_OBJECT_LOSS_LAUNCH
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }

@@ -13,6 +13,11 @@
 // corner_uncertainty (only with corner_offset); cfg.ch[i] == -1 marks an absent one.  Its channels are never read, the terms and
 // logged values that need it come out 0, and the rest follows the reference's `if self.depth_with_uncertainty` /
 // `compute_keypoint_corner` / `corner_with_uncertainty` branches (head_set_error below lists what each set can serve).
+//
+// Loss types (MODEL.HEAD.LOSS_TYPE entries 1 and 3; C ABI mfx_object_loss_types): the regular regression loss is L1 or smooth-L1
+// (reg_loss below: the offset coordinates, the dimensions, the corner coordinates, the keypoint depths, the combined depth), the
+// direct-depth loss is L1, log-L1 or the reference's `inv_sig` (depth_loss below).  Both kinds are template parameters of
+// object_terms_t: <REG_L1, DEP_L1> compiles to the expressions that were here before them (mfx_object_loss: same bits).
 #pragma once
 #include <cmath>
 
@@ -82,6 +87,28 @@ MFX_HD Dual datan2(Dual y, Dual x) {
 MFX_HD Dual dsqrt(Dual a) { const float s = sqrtf(a.v); return Dual{s, s > 0.f ? 0.5f * a.d / s : 0.f}; }
 MFX_HD Dual dsigmoid(Dual a) { const float s = 1.f / (1.f + expf(-a.v)); return Dual{s, s * (1.f - s) * a.d}; }
 
+// F.smooth_l1_loss at its default beta = 1 (value 0.5 and slope +-1 from both sides at |d| = 1: C1)
+MFX_HD Dual dsmooth_l1(Dual a) {
+    const float m = fabsf(a.v);
+    return m < 1.f ? Dual{0.5f * a.v * a.v, a.v * a.d} : Dual{m - 0.5f, a.v > 0.f ? a.d : -a.d};
+}
+
+// MODEL.HEAD.LOSS_TYPE[1]: 'L1', or any other string = F.smooth_l1_loss (detector_loss.py:53); LOSS_TYPE[3]: 'L1', 'log', 'inv_sig'
+// (detector_loss.py:45-49; 'berhu' cannot run in the reference and is refused by Loss_Computation)
+enum { REG_L1 = 0, REG_SMOOTH_L1, NUM_REG_LOSS };
+enum { DEP_L1 = 0, DEP_LOG, DEP_INV_SIG, NUM_DEPTH_LOSS };
+MFX_HD bool loss_kinds_ok(int reg, int dep) { return reg >= 0 && reg < NUM_REG_LOSS && dep >= 0 && dep < NUM_DEPTH_LOSS; }
+// the regular regression loss of a difference d (self.reg_loss_fnc, reduction 'none')
+template <int REG> MFX_HD Dual reg_loss(Dual d) { return REG == REG_L1 ? dabs(d) : dsmooth_l1(d); }
+// the direct-depth loss of (decoded, clamped prediction p; target t).  DEP_LOG: |log p - log t| (depth_losses.py Log_L1_Loss).
+// DEP_INV_SIG: what Inverse_Sigmoid_Loss.forward computes, |1/sigmoid(t) - 1 - t| -- a function of the TARGET alone (the reference
+// transforms `target`, not `prediction`): the depth channel gets a zero gradient, the depth uncertainty still gets its own.
+template <int DEP> MFX_HD Dual depth_loss(Dual p, float t) {
+    if (DEP == DEP_LOG) return dabs(dlog(p) - logf(t));
+    if (DEP == DEP_INV_SIG) return K(fabsf(1.f / (1.f / (1.f + expf(-t))) - 1.f - t));
+    return dabs(p - t);
+}
+
 struct Vec3 { Dual x, y, z; };
 
 // anno_encoder.py:124-140
@@ -106,8 +133,8 @@ MFX_HD Vec3 box_corner(int k, Dual cs, Dual sn, const Dual* dims, const Vec3& lo
 // One object.  X(ch) returns channel `ch` of the regression channels at the object's pixel as a Dual seeded for this lane;
 // `t` is the target row, `nrm` the eight batch-wide selection counts.  out[NVAL] ACCUMULATES nothing: it is overwritten with this
 // object's contribution to each loss term (already weighted and divided by its count) and to each logged mean.
-template <typename Reader>
-MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_cfg& c, const float* nrm, Dual* out) {
+template <int REG, int DEP, typename Reader>
+MFX_HD void object_terms_t(const Reader& X, const float* t, const mfx_object_loss_cfg& c, const float* nrm, Dual* out) {
     for (int i = 0; i < NVAL; ++i) out[i] = K(0.f);
     if (t[R_VALID] == 0.f) return;
     const float PI = 3.14159265358979323846f;
@@ -197,13 +224,13 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
 
     // ---- depth with aleatoric uncertainty (detector_loss.py:302-314) -----------------------------------------------------------
     {
-        const Dual l1 = dabs(p_depth - t_depth) * c.w[T_DEPTH];
+        const Dual l1 = depth_loss<DEP>(p_depth, t_depth) * c.w[T_DEPTH];
         out[T_DEPTH] = (has_du ? l1 * dexp(-d_unc) + d_unc * c.w[T_DEPTH] : l1) * inv_v;
         out[V_REAL_DEPTH] = K(l1.v * inv_v);
     }
     // ---- projected-centre offset; truncated objects optionally in their own (log) term -----------------------------------------
     {
-        const Dual l1 = dabs(ox - t[R_OFF]) + dabs(oy - t[R_OFF + 1]);
+        const Dual l1 = reg_loss<REG>(ox - t[R_OFF]) + reg_loss<REG>(oy - t[R_OFF + 1]);
         const bool trunc = t[R_TRUNC] != 0.f;
         if (c.separate_trunc) {
             if (trunc) out[T_TRUNC_OFFSET] = (c.trunc_log ? dlog(l1 + 1.f) : l1) * (c.w[T_TRUNC_OFFSET] / cnt(N_TRUNC));
@@ -233,7 +260,7 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
     // ---- dimensions ------------------------------------------------------------------------------------------------------------
     {
         Dual l = K(0.f);
-        for (int k = 0; k < 3; ++k) l = l + dabs(p_dims[k] - t[R_DIMS + k]) * c.dim_weight[k];
+        for (int k = 0; k < 3; ++k) l = l + reg_loss<REG>(p_dims[k] - t[R_DIMS + k]) * c.dim_weight[k];
         out[T_DIMS] = l * (c.w[T_DIMS] * inv_v);
     }
     // ---- eight box corners, L1 per coordinate, mean over corners (detector_loss.py:338-339) -------------------------------------
@@ -244,7 +271,7 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
         Dual l = K(0.f);
         for (int k = 0; k < 8; ++k) {
             const Vec3 a = box_corner(k, pc, ps, p_dims, p_loc), b = box_corner(k, tc, ts, t_dims, t_loc);
-            l = l + dabs(a.x - b.x) + dabs(a.y - b.y) + dabs(a.z - b.z);
+            l = l + reg_loss<REG>(a.x - b.x) + reg_loss<REG>(a.y - b.y) + reg_loss<REG>(a.z - b.z);
         }
         out[T_CORNER] = l * (c.w[T_CORNER] * inv_v / 8.f);
         // the logged 3D IoU of the same two boxes (detector_loss.py:333,436 get_iou_3d): values only, no tangent
@@ -267,11 +294,11 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
         for (int g = 0; g < 3; ++g) {
             const float wk = c.w[T_KEYPOINT_DEPTH];
             if (t[R_KDM + g] != 0.f) {
-                const Dual l1 = dabs(kd[g] - t_depth) * wk;
+                const Dual l1 = reg_loss<REG>(kd[g] - t_depth) * wk;
                 l = l + (has_cu ? l1 * dexp(-c_unc[g]) + c_unc[g] * wk : l1) / cnt(N_KD_VALID);
                 lg += l1.v / cnt(N_KD_VALID);
             } else if (c.modify_invalid) {
-                const Dual l1 = dabs(detach(kd[g]) - t_depth) * wk;
+                const Dual l1 = reg_loss<REG>(detach(kd[g]) - t_depth) * wk;
                 l = l + (has_cu ? l1 * dexp(-c_unc[g]) : l1) / cnt(N_KD_INVALID);
             }
         }
@@ -279,7 +306,7 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
         out[V_VALID_KD] = K(lg);
     }
     // ---- the combined depth ----------------------------------------------------------------------------------------------------
-    if (has_cu) out[T_SOFT_DEPTH] = dabs(soft - t_depth) * (c.w[T_SOFT_DEPTH] * inv_v);
+    if (has_cu) out[T_SOFT_DEPTH] = reg_loss<REG>(soft - t_depth) * (c.w[T_SOFT_DEPTH] * inv_v);
     // ---- logged relative depth errors (detector_loss.py:396-482) ---------------------------------------------------------------
     {
         const float mae[4] = {fabsf(p_depth.v - t_depth) / t_depth, fabsf(kd[0].v - t_depth) / t_depth, fabsf(kd[1].v - t_depth) / t_depth,
@@ -297,6 +324,19 @@ MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_
         }
     }
 }
+
+// L1 + L1 (LOSS_TYPE of runs/monoflex.yaml): mfx_object_loss
+template <typename Reader>
+MFX_HD void object_terms(const Reader& X, const float* t, const mfx_object_loss_cfg& c, const float* nrm, Dual* out) {
+    object_terms_t<REG_L1, DEP_L1>(X, t, c, nrm, out);
+}
+
+// MFX_LOSS_KINDS(reg, dep, CALL): CALL(REG, DEP) with the two run-time kinds as compile-time constants (loss_kinds_ok checked by the caller)
+#define MFX_LOSS_KINDS(reg, dep, CALL)                                                                                      \
+    switch ((reg) * mfx::oloss::NUM_DEPTH_LOSS + (dep)) {                                                                   \
+        case 0: CALL(0, 0); break; case 1: CALL(0, 1); break; case 2: CALL(0, 2); break;                                    \
+        case 3: CALL(1, 0); break; case 4: CALL(1, 1); break; default: CALL(1, 2); break;                                   \
+    }
 
 // the eight batch-wide selection counts, accumulated row by row (callers reduce over rows)
 MFX_HD void row_counts(const float* t, float* n) {

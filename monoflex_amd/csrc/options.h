@@ -125,7 +125,9 @@
     X(dcn_bt_sample, "launches of dcn_bwd_sample_kernel") \
     X(dcn_bt_far, "launches of dcn_bwd_far_kernel + dcn_bwd_far_fly_kernel") \
     X(gram, "phase calls of mfx_gram_heads on 16-bit maps") \
-    X(adamw_multi, "calls of mfx_adamw_multi")
+    X(adamw_multi, "calls of mfx_adamw_multi") \
+    X(optim_multi, "calls of mfx_optim_multi (the one-launch update with a rule / a gradient coefficient)") \
+    X(grad_norm_multi, "calls of mfx_grad_norm_multi")
 
 #define MFX_DECLARE_OPTION(name, def, lo, hi, doc) extern int g_opt_##name;
 #define MFX_DECLARE_COUNTER(name, doc) extern long g_cnt_##name;

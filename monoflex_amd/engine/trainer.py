@@ -387,8 +387,7 @@ class GraphedTrainStep:
         """[unscale + non-finite check,] [clip,] optimizer step [, loss-scale update] on the step's final gradients."""
         if self.scaler is not None:
             self.scaler.unscale_([self.flat] if self.flat is not None else [p.grad for p in self.net.parameters() if p.grad is not None])
-        self._clip()
-        optimizer_step(self.optimizer)
+        optimizer_step(self.optimizer, self._clip())
         if self.scaler is not None:
             self.scaler.update()
 
@@ -429,8 +428,8 @@ class GraphedTrainStep:
             p.grad = v
 
     def _clip(self):
-        if self.grad_norm_clip > 0:                                       # (device-side: total norm, clamp and scale without a host sync)
-            torch.nn.utils.clip_grad_norm_([p for p in self.net.parameters() if p.grad is not None], self.grad_norm_clip, foreach=True)
+        """-> the max norm that `optimizer_step` still has to apply, or -1."""
+        return clip_gradients(self.optimizer, self.net.parameters(), self.grad_norm_clip, foreach=True)
 
     def _exchange(self, k):
         """All-reduce (mean) of slice k.  GPU: enqueued on the comm stream behind everything the compute stream holds so far, so it
@@ -622,14 +621,26 @@ def train_step(model, optimizer, images, targets, grad_norm_clip=-1.0, scheduler
     (losses if scaler is None else scaler.scale_loss(losses)).backward()
     if scaler is not None:
         scaler.unscale_([p.grad for p in model.parameters() if p.grad is not None])
-    if grad_norm_clip > 0:
-        torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], grad_norm_clip)
-    optimizer_step(optimizer)
+    optimizer_step(optimizer, clip_gradients(optimizer, model.parameters(), grad_norm_clip))
     if scaler is not None:
         scaler.update()
     if scheduler is not None:
         scheduler.step()
     return losses.detach(), loss_dict, log_loss_dict
+
+
+def clip_gradients(optimizer, parameters, grad_norm_clip, foreach=None):
+    """SOLVER.GRAD_NORM_CLIP (reference engine/trainer.py:119).  Whenever the one-launch optimizer is taken the clip is part of it -- norm and coefficient
+    from fixed-order kernels over the optimizer's own pointer tables, the scaling inside the update (solver.MultiTensorAdamW.step; p.grad keeps the
+    unclipped values) -- eagerly and inside captures alike, so a replayed and an eager step stay the same arithmetic: this returns the max norm for
+    `optimizer_step` to apply.  Otherwise torch's clip_grad_norm_ runs here and -1 is returned.  <= 0 (every shipped config): nothing is launched."""
+    if not grad_norm_clip > 0:
+        return -1.0
+    from ..solver import multi_tensor_driver
+    if multi_tensor_driver(optimizer) is not None:
+        return float(grad_norm_clip)
+    torch.nn.utils.clip_grad_norm_([p for p in parameters if p.grad is not None], grad_norm_clip, foreach=foreach)    # (device-side: no host sync)
+    return -1.0
 
 
 def advance_schedule(iteration, warmup_iters, scheduler, warmup_scheduler):

@@ -126,6 +126,9 @@ class ObjectLossCfg(ctypes.Structure):                          # mfx_object_los
         [(n, c_float) for n in ("unc_lo", "unc_hi", "down_ratio", "eps")] + \
         [(n, c_int) for n in ("depth_mode", "has_depth_range", "dim_exp", "dim_use_std", "iou_type", "corner_depth_mode",
                               "separate_trunc", "trunc_log", "modify_invalid")] + [("ch", c_int * 9), ("reg_width", c_int)]
+    # the two loss kinds of mfx_object_loss_types travel BESIDE the struct (its layout is fixed): plain Python attributes of this object, not fields
+    reg_loss = 0                                                # index into REG_LOSSES
+    depth_loss = 0                                              # index into DEPTH_LOSSES
 
 
 class DecodeCfg(ctypes.Structure):                              # mfx_decode_cfg
@@ -183,6 +186,9 @@ SYMBOLS = {
     "mfx_pack_conv_weight": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     "mfx_adamw_chunk_elems": (_I, []),
     "mfx_adamw_multi": (_I, [_P, _P, _I, ctypes.c_longlong, _P, _P, _P]),
+    "mfx_optim_multi": (_I, [_P, _P, _I, ctypes.c_longlong, _P, _I, _P, _P, _P]),
+    "mfx_grad_norm_workspace_bytes": (_S, [ctypes.c_longlong]),
+    "mfx_grad_norm_multi": (_I, [_P, _P, _I, ctypes.c_longlong, _F, _P, _S, _P, _P, _P]),
     "mfx_colsum": (_I, [_P, _P, ctypes.c_long, _I, _I, _I, _P]),
     "mfx_colsum_add": (_I, [_P, _P, ctypes.c_long, _I, _I, _I, _P]),
     "mfx_bn_stats": (_I, [_P, _P, _P, ctypes.c_long, _I, _I, _P]),
@@ -220,6 +226,7 @@ SYMBOLS = {
     "mfx_dcn_backward_v2_rt": (_I, [_P] * 6 + [_I] + [_P] * 2 + [_I] * 6 + [_P, _S, _P]),
     "mfx_focal_loss": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
     "mfx_object_loss": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, ctypes.POINTER(ObjectLossCfg), _P, _P, _P]),
+    "mfx_object_loss_types": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, ctypes.POINTER(ObjectLossCfg), _I, _I, _P, _P, _P]),
     "mfx_object_loss_backward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "mfx_object_loss_backward_width": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "mfx_box3d_iou_pairs": (_I, [_P, _P, _I, _I, _P, _P]),
@@ -262,6 +269,11 @@ def head_decode_settings(cfg):
 HEAD_KEYS = ('2d_dim', '3d_offset', 'corner_offset', 'corner_uncertainty', '3d_dim', 'ori_cls', 'ori_offset', 'depth', 'depth_uncertainty')
 HEAD_WIDTHS = dict(zip(HEAD_KEYS, (4, 2, 20, 3, 3, 8, 8, 1, 1)))
 HEAD_OPTIONAL = ('depth_uncertainty', 'corner_offset', 'corner_uncertainty')
+# MODEL.HEAD.LOSS_TYPE entries 1 and 3 as mfx_object_loss_types numbers them (csrc/object_loss_math.h REG_* / DEP_*).  Entry 1: 'L1', or ANY other
+# string = F.smooth_l1_loss (reference detector_loss.py:53).  Entry 3: 'berhu' is not served (the reference's Berhu_Loss cannot run), see Loss_Computation.
+REG_LOSSES = ('L1', 'smooth_l1')
+DEPTH_LOSSES = ('L1', 'log', 'inv_sig')
+OPTIM_ADAMW, OPTIM_ADAM_L2 = 0, 1                                # mfx_optim_multi `rule`
 CORNER_DEPTHS = ('direct', 'keypoint_mean', 'soft_combine', 'hard_combine')        # mfx_object_loss_cfg.corner_depth_mode
 LOSS_REQUIRED = ('hm_loss', 'bbox_loss', 'depth_loss', 'offset_loss', 'orien_loss', 'dims_loss')
 LOSS_OPTIONAL = ('corner_loss', 'trunc_offset_loss', 'keypoint_loss', 'keypoint_depth_loss', 'weighted_avg_depth_loss')

@@ -52,10 +52,28 @@ class Loss_Computation:
         self.uncertainty_range = H.UNCERTAINTY_RANGE
         self.focal_alpha, self.focal_beta = H.LOSS_PENALTY_ALPHA, H.LOSS_BETA
         lt = list(H.LOSS_TYPE)
-        if H.HEATMAP_TYPE != 'centernet' or lt[1] != 'L1' or lt[3] != 'L1' or lt[2] not in ('giou', 'iou', 'linear_iou'):
+        if H.HEATMAP_TYPE != 'centernet' or lt[2] not in ('giou', 'iou', 'linear_iou'):
             raise NotImplementedError("loss types %s / heatmap %s: runs/monoflex.yaml uses centernet focal + L1 + giou + L1"
                                       % (lt, H.HEATMAP_TYPE))
         self.iou_type = lt[2]
+        # LOSS_TYPE[1], the regular regression loss, as the reference reads it (detector_loss.py:53): 'L1', or else F.smooth_l1_loss (beta 1).
+        # It applies wherever the reference calls reg_loss_fnc: offset, dimensions, corners, keypoint depths, the combined depth -- not to the
+        # keypoints (always L1), the multi-bin residuals or the direct depth.  LOSS_TYPE[0] is not read by the reference.
+        self.reg_loss = 'L1' if lt[1] == 'L1' else 'smooth_l1'
+        # LOSS_TYPE[3], the direct-depth loss (detector_loss.py:45-49, depth_losses.py).  'log' = |log p - log t| on the decoded, clamped depth.
+        # 'inv_sig' is ACCEPTED and served as the reference computes it: Inverse_Sigmoid_Loss.forward transforms the TARGET, |1/sigmoid(t) - 1 - t|,
+        # so the term does not depend on the prediction -- the depth channel gets a zero gradient, the depth uncertainty still gets its own.
+        # (Log_L1_Loss.forward and Inverse_Sigmoid_Loss.forward take no `reduction` keyword either, so detector_loss.py:299 raises TypeError on
+        # them as written; both compute the unreduced loss that `reduction='none'` asks for, and that arithmetic is what is served and what
+        # tests/golden/loss_types.npz records: tools/gen_loss_types_golden.py.)
+        # 'berhu' is REFUSED: the reference's Berhu_Loss.forward opens pdb.set_trace(), takes no `reduction` argument and returns a reduced sum, so
+        # the reference cannot train with it (although it is the value in the reference's config/defaults.py).  Anything else: ValueError, as there.
+        if lt[3] == 'berhu':
+            raise NotImplementedError("MODEL.HEAD.LOSS_TYPE[3] 'berhu' (the value in the reference's config/defaults.py): the reference's Berhu_Loss.forward "
+                                      "opens pdb.set_trace() and takes no `reduction` argument, so the reference cannot train with it; use 'L1', 'log' or 'inv_sig'")
+        if lt[3] not in ('L1', 'log', 'inv_sig'):
+            raise ValueError("MODEL.HEAD.LOSS_TYPE[3] %r: the depth loss is 'L1', 'log' or 'inv_sig' ('berhu' cannot run in the reference)" % (lt[3],))
+        self.depth_loss = lt[3]
         if cfg.INPUT.ORIENTATION != 'multi-bin':
             raise NotImplementedError("orientation loss: the multi-bin encoding of runs/monoflex.yaml")
         self.orien_bin_size = cfg.INPUT.ORIENTATION_BIN_SIZE
@@ -158,8 +176,28 @@ class Loss_Computation:
         for i, key in enumerate(L.HEAD_KEYS):
             c.ch[i] = self.head_set.ch(key)                   # -1: the set does not have this (optional) head
         c.reg_width = self.head_set.R
+        c.reg_loss, c.depth_loss = L.REG_LOSSES.index(self.reg_loss), L.DEPTH_LOSSES.index(self.depth_loss)      # beside the struct, not in it
         self._obj_cfg = c
         return c
+
+    def object_loss_kinds(self):
+        """(reg_loss, depth_loss) of this evaluator as mfx_object_loss_types numbers them: they travel beside object_loss_cfg()."""
+        from ... import lib as L
+        return L.REG_LOSSES.index(self.reg_loss), L.DEPTH_LOSSES.index(self.depth_loss)
+
+    def _reg_l(self, d):
+        """self.reg_loss_fnc(pred, target, reduction='none') of the difference d = pred - target."""
+        if self.reg_loss == 'L1':
+            return d.abs()
+        return F.smooth_l1_loss(d, torch.zeros_like(d), reduction='none')
+
+    def _depth_l(self, p, t, t_safe):
+        """self.depth_loss(pred, target, reduction='none'); `t_safe` = the target with 1 on unselected rows (no log(0) behind a zero weight)."""
+        if self.depth_loss == 'log':
+            return (torch.log(p) - torch.log(t_safe)).abs()
+        if self.depth_loss == 'inv_sig':                      # of the target alone, as the reference computes it (see __init__)
+            return (1 / torch.sigmoid(t) - 1 - t).abs() + 0 * p
+        return (p - t).abs()
 
     # ---- Anno_Encoder pieces, batched over all B*MAX_OBJECTS rows --------------------------------------
     def _decode_depth(self, off):                                                 # anno_encoder.py:124-140
@@ -362,11 +400,12 @@ class Loss_Computation:
             rows = self.pack_objects(tv)
         if cfg is None or rows is None:
             raise NotImplementedError("fused object loss: 4 orientation bins, 10 keypoints, a depth range")
+        kinds = self.object_loss_kinds()
         if predictions.get('reg') is None:
-            terms, logged = AG.ObjectLossFn.apply(predictions['reg_rows'].float(), rows.to(dev), cfg, 0)      # (N,R): row n = object row n
+            terms, logged = AG.ObjectLossFn.apply(predictions['reg_rows'].float(), rows.to(dev), cfg, 0, *kinds)      # (N,R): row n = object row n
         else:
             reg = predictions['reg'].permute(0, 2, 3, 1)                          # the predictor's NHWC map: a view
-            terms, logged = AG.ObjectLossFn.apply(reg.float(), rows.to(dev), cfg, 0)
+            terms, logged = AG.ObjectLossFn.apply(reg.float(), rows.to(dev), cfg, 0, *kinds)
         t = terms.unbind(0)
         loss_dict = _LossDict({'hm_loss': self._heat_term(predictions, heat, dev), 'bbox_loss': t[0], 'dims_loss': t[5], 'orien_loss': t[4],
                                'offset_loss': t[2]})
@@ -433,7 +472,7 @@ class Loss_Computation:
         depth_MAE = (P['depth_3D'] - T['depth_3D']).abs() / t_depth_safe
 
         # direct depth with aleatoric uncertainty
-        d_l1 = W['depth_loss'] * (P['depth_3D'] - T['depth_3D']).abs()
+        d_l1 = W['depth_loss'] * self._depth_l(P['depth_3D'], T['depth_3D'], t_depth_safe)
         real_depth_loss = _wmean(d_l1.detach(), v)
         hs = self.head_set
         has = lambda name: name in self.loss_keys                                  # noqa: E731
@@ -443,7 +482,7 @@ class Loss_Computation:
             depth_loss = _wmean(d_l1, v)
 
         # projected-centre offset: L1 inside, log(1+L1) for truncated objects
-        off_l1 = (P['offset_3D'] - T['offset_3D']).abs().sum(dim=1)
+        off_l1 = self._reg_l(P['offset_3D'] - T['offset_3D']).sum(dim=1)
         trunc = T['trunc_mask_3D'].float()
         if self.separate_trunc_offset:
             tl = off_l1 if self.trunc_offset_loss_type == 'L1' else torch.log(1 + off_l1)
@@ -453,7 +492,7 @@ class Loss_Computation:
             offset_loss = W['offset_loss'] * _wmean(off_l1, v)
 
         orien_loss = W['orien_loss'] * self._multibin(P['orien_3D'], T['orien_3D'], v)
-        dims_l1 = (P['dims_3D'] - T['dims_3D']).abs() * self._const('dim_weight', self.dim_weight, dev)
+        dims_l1 = self._reg_l(P['dims_3D'] - T['dims_3D']) * self._const('dim_weight', self.dim_weight, dev)
         dims_loss = W['dims_loss'] * _wmean(dims_l1.sum(dim=1), v)
         loss_dict = {'hm_loss': hm_loss, 'bbox_loss': reg_2D_loss, 'dims_loss': dims_loss, 'orien_loss': orien_loss,
                      'offset_loss': offset_loss}
@@ -461,7 +500,7 @@ class Loss_Computation:
             loss_dict['trunc_offset_loss'] = trunc_offset_loss
         if has('corner_loss'):
             # (N,8) per-corner L1 sums averaged over all N*8 entries (detector_loss.py:338-339: `.sum(dim=2).mean()`)
-            loss_dict['corner_loss'] = W['corner_loss'] * _wmean((P['corners_3D'] - T['corners_3D']).abs().sum(dim=2).mean(dim=1), v)
+            loss_dict['corner_loss'] = W['corner_loss'] * _wmean(self._reg_l(P['corners_3D'] - T['corners_3D']).sum(dim=2).mean(dim=1), v)
         loss_dict['depth_loss'] = depth_loss
         mae = {'depth_MAE': _wmean(depth_MAE.detach(), v)}
         log_valid_kd = None
@@ -476,8 +515,8 @@ class Loss_Computation:
             if has('keypoint_depth_loss'):
                 km = (T['keypoints_depth_mask'] & valid[:, None]).float()
                 kinv = ((~T['keypoints_depth_mask']) & valid[:, None]).float()
-                kd_valid = W['keypoint_depth_loss'] * (kd - t_kd).abs()
-                kd_invalid = W['keypoint_depth_loss'] * (kd.detach() - t_kd).abs()
+                kd_valid = W['keypoint_depth_loss'] * self._reg_l(kd - t_kd)
+                kd_invalid = W['keypoint_depth_loss'] * self._reg_l(kd.detach() - t_kd)
                 log_valid_kd = _wmean(kd_valid.detach(), km)
                 if hs.cu:
                     unc = P['corner_offset_uncertainty']
@@ -503,7 +542,7 @@ class Loss_Computation:
             cw = cw / cw.sum(dim=1, keepdim=True)
             soft_depths = torch.sum(comb_depth * cw, dim=1)
             if has('weighted_avg_depth_loss'):
-                loss_dict['weighted_avg_depth_loss'] = W['weighted_avg_depth_loss'] * _wmean((soft_depths - T['depth_3D']).abs(), v)
+                loss_dict['weighted_avg_depth_loss'] = W['weighted_avg_depth_loss'] * _wmean(self._reg_l(soft_depths - T['depth_3D']), v)
             with torch.no_grad():
                 hard = cMAE.gather(1, comb_unc.argmin(dim=1, keepdim=True)).squeeze(1)
                 mae.update({'lower_MAE': _wmean(cMAE.min(dim=1)[0], v), 'hard_MAE': _wmean(hard, v),

@@ -50,12 +50,15 @@ def get_model_params(model, cfg, per_parameter_groups=False, tensor_lr_device=No
 
 def build_optimizer(model, cfg, per_parameter_groups=False, capturable=None):
     """`capturable=None`: capturable (device-side step counters and learning rates) whenever the model lives on a GPU, so that the
-    training loop can replay the step from hipGraphs (engine/trainer.do_train); the arithmetic is AdamW's either way."""
+    training loop can replay the step from hipGraphs (engine/trainer.do_train); the arithmetic is AdamW's / Adam's either way.
+    'adam' is the reference's optim.Adam(betas=(0.9, 0.99)) with L2 weight decay (solver/__init__.py:33-34); on the CPU it is built as a plain
+    torch.optim.Adam with float learning rates.  'sgd' stays eager: the reference's own sgd branch reads a MOMENTUM key its config does not define."""
     s = cfg.SOLVER
     dev = next((p.device for p in model.parameters() if p.is_cuda), None)
+    adam_family = s.OPTIMIZER in ("adamw", "adam")
     if capturable is None:
-        capturable = dev is not None and s.OPTIMIZER == "adamw"
-    tensor_lr = capturable and dev is not None and s.OPTIMIZER == "adamw"
+        capturable = dev is not None and adam_family
+    tensor_lr = capturable and dev is not None and adam_family
     params = get_model_params(model, cfg, per_parameter_groups, tensor_lr_device=dev if tensor_lr else None)
     on_gpu = dev is not None
     if s.OPTIMIZER == "adamw":
@@ -63,7 +66,10 @@ def build_optimizer(model, cfg, per_parameter_groups=False, capturable=None):
         return torch.optim.AdamW(params, lr=lr, weight_decay=s.WEIGHT_DECAY, betas=(0.9, 0.99), fused=on_gpu or None,
                                  capturable=capturable)
     if s.OPTIMIZER == "adam":
-        return torch.optim.Adam(params, lr=s.BASE_LR, weight_decay=s.WEIGHT_DECAY, betas=(0.9, 0.99), fused=on_gpu or None)
+        if not capturable:                                                # the CPU (or an explicit capturable=False): as before
+            return torch.optim.Adam(params, lr=s.BASE_LR, weight_decay=s.WEIGHT_DECAY, betas=(0.9, 0.99), fused=on_gpu or None)
+        lr = torch.tensor(float(s.BASE_LR), dtype=torch.float32, device=dev) if tensor_lr else s.BASE_LR
+        return torch.optim.Adam(params, lr=lr, weight_decay=s.WEIGHT_DECAY, betas=(0.9, 0.99), fused=on_gpu or None, capturable=True)
     if s.OPTIMIZER == "sgd":
         return torch.optim.SGD(params, lr=s.BASE_LR, weight_decay=s.WEIGHT_DECAY, momentum=s.get("MOMENTUM", 0.9))
     raise NotImplementedError("SOLVER.OPTIMIZER %r (adam_onecycle's fastai wrapper is not part of the adamw training contract)" % s.OPTIMIZER)
@@ -112,7 +118,14 @@ class MultiTensorAdamW:
     The kernel reads a pointer table on the device.  Eagerly the table is rebuilt and uploaded every call (gradients are fresh tensors each step).
     Inside a stream capture the addresses of the step's gradients are known once backward has been captured, but a host-to-device copy cannot be:
     the launch is recorded against tables of its own (allocated by the preceding eager step -- NOT inside the capture: see step() -- and never
-    reused by eager steps) and `finish_capture()` fills them once the capture has ended (before the first replay)."""
+    reused by eager steps) and `finish_capture()` fills them once the capture has ended (before the first replay).
+
+    `step(max_norm)` with max_norm > 0 is the CLIPPED update (reference engine/trainer.py:119 clip_grad_norm_, then step): two launches over the same
+    tables leave [total_norm, coef] in a device pair (`self.grad_norm`: mfx_grad_norm_multi, fixed-order sums, no atomics) and the update multiplies
+    every gradient element by coef as it reads it.  The gradients themselves are not written: p.grad keeps the UNCLIPPED values.
+    `MultiTensorAdam` below is the same driver for torch.optim.Adam with L2 weight decay (SOLVER.OPTIMIZER 'adam')."""
+    optimizer_type = torch.optim.AdamW
+    rule = 0                      # lib.OPTIM_ADAMW
 
     def __init__(self, optimizer):
         import weakref
@@ -121,12 +134,15 @@ class MultiTensorAdamW:
         self.pending = []
         self.captured = []
         self.spare = {}           # device -> a table set allocated by the last eager step for the next captured launch
+        self.grad_norm = None     # [total_norm, coef] of the last clipped step (device fp32 pair; a captured step keeps its own)
 
-    @staticmethod
-    def eligible(optimizer):
-        if type(optimizer) is not torch.optim.AdamW:
+    @classmethod
+    def eligible(cls, optimizer):
+        if type(optimizer) is not cls.optimizer_type:
             return False
         for g in optimizer.param_groups:
+            if bool(g.get("decoupled_weight_decay", cls.rule == 0)) != (cls.rule == 0):      # (torch.optim.Adam can be asked for AdamW's rule)
+                return False
             if not g.get("capturable") or g.get("amsgrad") or g.get("maximize") or not torch.is_tensor(g["lr"]) or not g["lr"].is_cuda \
                     or g["lr"].dtype != torch.float32 or g.get("differentiable"):
                 return False
@@ -138,8 +154,13 @@ class MultiTensorAdamW:
     def _new_tables(self, dev, n, ngroups):
         from . import lib as L
         cap = max(n, sum(len(g["params"]) for g in self._opt().param_groups))
+        chunk = L.load().mfx_adamw_chunk_elems()
+        nchunk = sum((p.numel() + chunk - 1) // chunk for g in self._opt().param_groups for p in g["params"])
+        # ... + the gradient norm's partial sums (one float per chunk) and its [total_norm, coef] pair: written and read by the launches themselves
         return (torch.zeros(cap * ctypes_sizeof(L.AdamWDesc), dtype=torch.uint8, device=dev), torch.zeros(cap + 1, dtype=torch.int64, device=dev),
-                torch.zeros(max(ngroups, len(self._opt().param_groups)) * ctypes_sizeof(L.AdamWGroup), dtype=torch.uint8, device=dev), cap)
+                torch.zeros(max(ngroups, len(self._opt().param_groups)) * ctypes_sizeof(L.AdamWGroup), dtype=torch.uint8, device=dev), cap,
+                torch.zeros(int(L.load().mfx_grad_norm_workspace_bytes(nchunk)), dtype=torch.uint8, device=dev),
+                torch.ones(2, dtype=torch.float32, device=dev))
 
     def _tables(self, dev, n, ngroups):
         from . import lib as L
@@ -149,7 +170,7 @@ class MultiTensorAdamW:
         return t
 
     @torch.no_grad()
-    def step(self):
+    def step(self, max_norm=-1.0):
         import numpy as np
         from . import lib as L
         opt = self._opt()
@@ -171,6 +192,9 @@ class MultiTensorAdamW:
         found_inf = getattr(opt, "found_inf", None)
         opt._opt_called = True                                         # (what torch's wrapped step() tells the LR schedulers)
         capturing = torch.cuda.is_current_stream_capturing()
+        clip = max_norm is not None and float(max_norm) > 0
+        if clip and len(by_dev) > 1:
+            raise RuntimeError("MultiTensorAdamW: the clipped update takes the norm over ONE device's gradients")
         for dev, items in by_dev.items():
             n = len(items)
             descs = (L.AdamWDesc * n)()
@@ -194,18 +218,27 @@ class MultiTensorAdamW:
                 sp = self.spare.pop(dev, None)
                 if sp is None or sp[3] < n:
                     raise RuntimeError("MultiTensorAdamW: run one eager optimizer step before capturing one (it allocates the captured launch's tables)")
-                dt, pt, gt = sp[:3]
+                dt, pt, gt, _, ws, out2 = sp
                 self.captured.append(sp)
                 self.pending.append((dt, pt, gt, host))
             else:
-                dt, pt, gt, _ = self._tables(dev, n, len(opt.param_groups))
+                dt, pt, gt, _, ws, out2 = self._tables(dev, n, len(opt.param_groups))
                 self._upload(dt, pt, gt, host)
                 if dev not in self.spare:
                     self.spare[dev] = self._new_tables(dev, n, len(opt.param_groups))
+            fi = ctypes_ptr(found_inf) if found_inf is not None else None
             with torch.cuda.device(dev):
-                L.check(L.load().mfx_adamw_multi(ctypes_ptr(dt), ctypes_ptr(pt), n, int(prefix[n]), ctypes_ptr(gt),
-                                                 ctypes_ptr(found_inf) if found_inf is not None else None,
-                                                 ctypes_stream()), "mfx_adamw_multi")
+                coef = None
+                if clip:
+                    L.check(L.load().mfx_grad_norm_multi(ctypes_ptr(dt), ctypes_ptr(pt), n, int(prefix[n]), float(max_norm), ctypes_ptr(ws), ws.numel(),
+                                                         ctypes_ptr(out2), fi, ctypes_stream()), "mfx_grad_norm_multi")
+                    self.grad_norm = out2
+                    coef = ctypes_ptr(out2[1:])
+                if self.rule == L.OPTIM_ADAMW and coef is None:            # the plain AdamW step: the launch it has always been
+                    L.check(L.load().mfx_adamw_multi(ctypes_ptr(dt), ctypes_ptr(pt), n, int(prefix[n]), ctypes_ptr(gt), fi, ctypes_stream()), "mfx_adamw_multi")
+                else:
+                    L.check(L.load().mfx_optim_multi(ctypes_ptr(dt), ctypes_ptr(pt), n, int(prefix[n]), ctypes_ptr(gt), self.rule, coef, fi, ctypes_stream()),
+                            "mfx_optim_multi")
 
     @staticmethod
     def _upload(dt, pt, gt, host):
@@ -220,6 +253,28 @@ class MultiTensorAdamW:
         self.pending = []
         if torch.cuda.is_available():
             torch.cuda.synchronize()
+
+
+class MultiTensorAdam(MultiTensorAdamW):
+    """The same driver for torch.optim.Adam (fused, capturable, device-scalar learning rates: `build_optimizer` with SOLVER.OPTIMIZER 'adam' on a GPU):
+    L2 weight decay, g' = g + wd p, the arithmetic of torch's capturable `_fused_adam_` (mfx_optim_multi, rule MFX_OPTIM_ADAM_L2).  The state is torch's
+    own {step, exp_avg, exp_avg_sq}, so state_dict() loads into a plain torch.optim.Adam."""
+    optimizer_type = torch.optim.Adam
+    rule = 1                      # lib.OPTIM_ADAM_L2
+
+
+def multi_tensor_driver(optimizer):
+    """The one-launch driver of `optimizer` (created on first use and kept on it), or None: not a GPU AdamW / Adam of `build_optimizer`'s making, or
+    MFX_HIP_ADAMW=0 (torch's own kernels)."""
+    if not HIP_ADAMW[0]:
+        return None
+    mt = getattr(optimizer, "_mfx_multi", None)
+    if mt is None:
+        for cls in (MultiTensorAdamW, MultiTensorAdam):
+            if cls.eligible(optimizer):
+                mt = optimizer._mfx_multi = cls(optimizer)
+                break
+    return mt
 
 
 def ctypes_sizeof(t):
@@ -240,15 +295,16 @@ def ctypes_stream():
 HIP_ADAMW = [__import__("os").environ.get("MFX_HIP_ADAMW", "1") != "0"]      # MFX_HIP_ADAMW=0: torch's own fused AdamW step (A/B)
 
 
-def optimizer_step(optimizer):
-    """`optimizer.step()`; a GPU AdamW built by `build_optimizer` takes the one-launch HIP form (MultiTensorAdamW) -- eagerly and inside captures alike,
-    so a replayed step and an eager step stay the same arithmetic."""
-    mt = getattr(optimizer, "_mfx_multi", None)
-    if mt is None and HIP_ADAMW[0] and MultiTensorAdamW.eligible(optimizer):
-        mt = optimizer._mfx_multi = MultiTensorAdamW(optimizer)
-    if mt is None or not HIP_ADAMW[0]:
+def optimizer_step(optimizer, max_norm=-1.0):
+    """`optimizer.step()`; a GPU AdamW / Adam built by `build_optimizer` takes the one-launch HIP form (MultiTensorAdamW / MultiTensorAdam) -- eagerly and
+    inside captures alike, so a replayed step and an eager step stay the same arithmetic.  `max_norm` > 0: the clipped update (gradient norm + coefficient
+    as part of that form); a caller whose optimizer has no such driver (`multi_tensor_driver` is None) clips with torch's function first and passes nothing."""
+    mt = multi_tensor_driver(optimizer)
+    if mt is None:
+        if max_norm is not None and float(max_norm) > 0:
+            raise ValueError("optimizer_step: max_norm needs the one-launch driver; clip with torch.nn.utils.clip_grad_norm_ first (engine/trainer.py)")
         return optimizer.step()
-    return mt.step()
+    return mt.step(max_norm)
 
 
 def finish_capture(optimizer):
