@@ -83,6 +83,7 @@ int mfx_commit_options(void);
  *   DCN backward: "dcn_bt_tile" (dcn_bwd_tile_kernel), "dcn_bt_sample" (dcn_bwd_sample_kernel), "dcn_bt_far" (far-corner kernels, both forms);
  *   "gram" (mfx_gram_heads phase calls), "adamw_multi" (one-launch AdamW), "optim_multi" (mfx_optim_multi: the one-launch update with a rule
  *   and / or a gradient coefficient), "grad_norm_multi" (mfx_grad_norm_multi: the gradient norm of the clipped update).
+ * Post-processing: "box_nms" (launches of mfx_box_nms: one per call that had rows, whatever B).
  * Unknown names return MFX_ERR_ARG (negative). */
 long mfx_get_counter(const char* name);
 
@@ -664,6 +665,25 @@ int mfx_object_loss_backward_width(const float* G, const float* gout_terms, cons
  *   iou   : fp32 [N] (overwritten).  A pair whose union is <= 0 or not finite gives 0, never NaN.
  * One lane per pair, one launch on `stream`, nothing allocated, no synchronisation; N == 0 returns MFX_OK without a launch. */
 int mfx_box3d_iou_pairs(const float* boxes_a, const float* boxes_b, int N, int form, float* iou, void* stream);
+
+/* Greedy suppression of duplicate detections per image (csrc/box_nms.hip, csrc/box_nms_math.h): TEST.USE_NMS '2d' / '3d', TEST.NMS_THRESH,
+ * TEST.NMS_CLASS_AGNOSTIC -- keys the reference declares (config/defaults.py) and reads nowhere, so the semantics are this library's:
+ *   det      : fp32 [B][K][14] rows of mfx_decode_boxes* (cls, alpha, x1, y1, x2, y2, h, w, l, x, y = bottom centre, z, ry, score), untouched
+ *   valid_in : int32 [B][K]; rows with 0 take no part and stay 0
+ *   order    : an image's valid rows by score (column 13) descending, equal scores by the lower slot k (a NaN score ranks last)
+ *   walk     : a row is kept unless an already KEPT row overlaps it with IoU > thresh (strict); a suppressed row suppresses nothing
+ *   classes  : class_agnostic == 0: only rows of equal class id (column 0) can suppress each other; != 0: any pair can
+ *   kind     : MFX_NMS_2D: axis-aligned IoU of columns 2:6 as the reference's box_iou (engine/visualize_infer.py:23-27): no +1, and a 0 / 0
+ *              overlap is NaN, which is not > thresh; MFX_NMS_3D: mfx_box3d_iou_pairs' form-0 arithmetic of the rows (x, y - h / 2, z, l, h, w, ry),
+ *              the pair of slots i < j evaluated once with row j as the origin
+ *   valid_out: int32 [B][K] = valid_in & kept (overwritten); may alias valid_in
+ * Checked before any device work: B, K < 0, an unknown kind, thresh outside [0, 1) (NaN too), a null pointer: MFX_ERR_ARG; K > 128:
+ * MFX_ERR_UNSUPPORTED.  B == 0 or K == 0 returns MFX_OK without a launch.  One launch of B 256-lane workgroups on `stream` (counter "box_nms"),
+ * no atomics, no workspace, nothing allocated, no synchronisation. */
+#define MFX_NMS_2D 1
+#define MFX_NMS_3D 2
+int mfx_box_nms(const float* det, const int32_t* valid_in, int B, int K, int kind, float thresh, int class_agnostic, int32_t* valid_out,
+                void* stream);
 
 /* Validation diagnostics at the ground-truth centres (csrc/eval_diag.hip, csrc/eval_diag_math.h; reference PostProcessor.evaluate_3D_depths,
  * model/head/detector_infer.py:280-359 = TEST.EVAL_DEPTH, and evaluate_3D_detection, :361-452 = TEST.EVAL_DIS_IOUS).  One lane per (image,

@@ -147,6 +147,9 @@ def _defaults():
         SINGLE_GPU_TEST=True, IMS_PER_BATCH=1, PRED_2D=True, UNCERTAINTY_AS_CONFIDENCE=False,
         METRIC=['R40'], EVAL_DIS_IOUS=False, EVAL_DEPTH=False, DETECTIONS_PER_IMG=50,
         DETECTIONS_THRESHOLD=0.1, VISUALIZE_THRESHOLD=0.4,
+        # declared by the reference (config/defaults.py) and read by none of its files; here USE_NMS '2d' / '3d' suppresses duplicate
+        # detections on the device (ops.box_nms).  EVAL_DEPTH_METHODS is accepted and, as there, never read.
+        USE_NMS='none', NMS_THRESH=-1., NMS_CLASS_AGNOSTIC=False, EVAL_DEPTH_METHODS=[],
     ))
     C.OUTPUT_DIR = "./tools/logs"
     C.SEED = -1

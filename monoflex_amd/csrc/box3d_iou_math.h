@@ -113,5 +113,65 @@ MFX_HD float iou_corners(const float* A, const float* B) {
     return iou_of(qa, qb, -0.25f * ya[0], -0.25f * ya[1], -0.25f * yb[0], -0.25f * yb[1]);
 }
 
+// ---- the same arithmetic with the clip's two vertex rings in the CALLER's memory ------------------------------------------------------
+// quad_intersection keeps its rings in a private array that is indexed at run time: a lane's 16 + 16 floats go to scratch memory (or to
+// LDS the compiler sets aside).  A kernel whose workgroup holds a table in LDS with the lane as the fastest index (box_nms.hip) passes
+// one column of it instead: 2 * 2 * MAXV floats, element k at buf[k * stride].  Statement for statement the functions above -- a host
+// build gives bit-identical results (tests/test_box_nms_cpu.py compares them) -- kept beside them so that the units that call the private
+// forms compile to the code they always did.
+MFX_HD float quad_intersection_in(const float* a, const float* b, float* buf, int stride) {
+    const float orient = shoelace2(b, 4) < 0.f ? -1.f : 1.f;
+    int n = 4, cur = 0;
+    for (int i = 0; i < 8; ++i) buf[i * stride] = a[i];
+    for (int e = 0; e < 4 && n > 0; ++e) {
+        const float ex = b[2 * e], ez = b[2 * e + 1];
+        const float dx = (b[2 * ((e + 1) & 3)] - ex) * orient, dz = (b[2 * ((e + 1) & 3) + 1] - ez) * orient;
+        const float* in = buf + cur * (2 * MAXV) * stride;
+        float* out = buf + (cur ^ 1) * (2 * MAXV) * stride;
+        int m = 0;
+        float px = in[2 * (n - 1) * stride], pz = in[(2 * (n - 1) + 1) * stride];
+        float pd = dx * (pz - ez) - dz * (px - ex);
+        for (int i = 0; i < n; ++i) {
+            const float qx = in[2 * i * stride], qz = in[(2 * i + 1) * stride];
+            const float qd = dx * (qz - ez) - dz * (qx - ex);
+            if ((pd >= 0.f) != (qd >= 0.f)) {
+                const float t = pd / (pd - qd);
+                if (m < MAXV) { out[2 * m * stride] = px + t * (qx - px); out[(2 * m + 1) * stride] = pz + t * (qz - pz); ++m; }
+            }
+            if (qd >= 0.f && m < MAXV) { out[2 * m * stride] = qx; out[(2 * m + 1) * stride] = qz; ++m; }
+            px = qx; pz = qz; pd = qd;
+        }
+        n = m;
+        cur ^= 1;
+    }
+    if (n < 3) return 0.f;
+    const float* p = buf + cur * (2 * MAXV) * stride;
+    float s = 0.f;                                                 // shoelace2 of the surviving ring
+    for (int i = 0; i < n; ++i) {
+        const int j = i + 1 < n ? i + 1 : 0;
+        s += p[2 * i * stride] * p[(2 * j + 1) * stride] - p[2 * j * stride] * p[(2 * i + 1) * stride];
+    }
+    return 0.5f * fabsf(s);
+}
+
+MFX_HD float iou_of_in(const float* qa, const float* qb, float lo_a, float hi_a, float lo_b, float hi_b, float* buf, int stride) {
+    const float h_ov = fmaxf(0.f, fminf(hi_a, hi_b) - fmaxf(lo_a, lo_b));
+    const float area_a = 0.5f * fabsf(shoelace2(qa, 4)), area_b = 0.5f * fabsf(shoelace2(qb, 4));
+    const float ov = h_ov > 0.f ? quad_intersection_in(qa, qb, buf, stride) * h_ov : 0.f;
+    const float uni = area_a * (hi_a - lo_a) + area_b * (hi_b - lo_b) - ov;
+    const float r = ov / uni;
+    return (uni > 0.f && r >= 0.f && r <= 3.4e38f) ? r : 0.f;
+}
+
+// iou_parts; iou_rows(a, b) is this with cosf / sinf of the two yaws
+MFX_HD float iou_parts_in(const float* loc_a, const float* dims_a, float cs_a, float sn_a,
+                          const float* loc_b, const float* dims_b, float cs_b, float sn_b, float* buf, int stride) {
+    float qa[8], qb[8];
+    bottom_quad(dims_a[0], dims_a[2], cs_a, sn_a, loc_a[0] - loc_b[0], loc_a[2] - loc_b[2], qa);
+    bottom_quad(dims_b[0], dims_b[2], cs_b, sn_b, 0.f, 0.f, qb);
+    const float ya = loc_a[1] - loc_b[1];
+    return iou_of_in(qa, qb, -(ya + 0.5f * dims_a[1]), -(ya - 0.5f * dims_a[1]), -(0.5f * dims_b[1]), 0.5f * dims_b[1], buf, stride);
+}
+
 }  // namespace biou
 }  // namespace mfx

@@ -108,6 +108,7 @@
     X(conv_splitk, "those that ran split-K") \
     X(conv_bn_stats, "convolutions whose epilogue accumulated the BatchNorm statistics") \
     X(edge_chain, "launches of the edge fusion's one-kernel conv chain (edge_chain.hip)") \
+    X(box_nms, "launches of the duplicate suppression (box_nms.hip): one per mfx_box_nms call that had rows, whatever B") \
     /* training-side families */ \
     X(wgrad_patch, "weight gradients by the LDS-patch kernel (wgrad_tr.hip)") \
     X(wgrad_tr, "weight gradients by the transposed-read kernel (wgrad_tr.hip)") \

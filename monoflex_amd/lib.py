@@ -230,6 +230,7 @@ SYMBOLS = {
     "mfx_object_loss_backward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "mfx_object_loss_backward_width": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "mfx_box3d_iou_pairs": (_I, [_P, _P, _I, _I, _P, _P]),
+    "mfx_box_nms": (_I, [_P, _P, _I, _I, _I, _F, _I, _P, _P]),
     "mfx_eval_diagnostics": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, ctypes.POINTER(DecodeCfg), ctypes.POINTER(HeadLayout), _I, _P, _P, _P, _P]),
     "mfx_kitti_encode_targets": (_I, [ctypes.POINTER(KittiDesc), _P]),
     "mfx_kitti_encode_targets_views": (_I, [ctypes.POINTER(KittiDesc), _P, _P]),
@@ -249,6 +250,9 @@ SYMBOLS = {
 
 # mfx_decode_boxes_mode's depth_mode (include/monoflex_hip.h MFX_DEPTH_*), by the reference's `output_depth` names (detector_infer.py:149-198)
 DEPTH_MODES = {"soft": 0, "hard": 1, "mean": 2, "direct": 3, "keypoints_avg": 4, "keypoints_center": 5, "keypoints_02": 6, "keypoints_13": 7}
+
+NMS_KINDS = {"2d": 1, "3d": 2}                                  # mfx_box_nms' `kind` (MFX_NMS_2D / MFX_NMS_3D) by TEST.USE_NMS value; 'none' launches nothing
+NMS_MAX_ROWS = 128                                              # its K limit
 
 DEPTH_DECODES = {"exp": 0, "linear": 1, "inv_sigmoid": 2}      # mfx_decode_cfg.depth_decode = mfx_object_loss_cfg.depth_mode (anno_encoder.py:124-140)
 

@@ -69,6 +69,20 @@ class PostProcessor(nn.Module):
         if self.eval_dis_iou and self.output_depth == 'oracle':
             raise NotImplementedError("TEST.EVAL_DIS_IOUS with OUTPUT_DEPTH 'oracle': the disentangled boxes take the depth of one decode mode "
                                       "(%s)" % ", ".join(L.DEPTH_MODES))
+        # TEST.USE_NMS / NMS_THRESH / NMS_CLASS_AGNOSTIC: declared by the reference (config/defaults.py) and read by none of its files.  Here
+        # '2d' / '3d' suppress duplicate detections on the device after the decode (ops.box_nms; the semantics are in INTEGRATION.md);
+        # 'none', the default, launches nothing.  A user who turns it on without a usable threshold is told.
+        self.use_nms, self.nms_thresh = cfg.TEST.USE_NMS, float(cfg.TEST.NMS_THRESH)
+        self.nms_class_agnostic = bool(cfg.TEST.NMS_CLASS_AGNOSTIC)
+        if self.use_nms != 'none' and self.use_nms not in L.NMS_KINDS:
+            raise ValueError("TEST.USE_NMS %r is not one of 'none', %s" % (self.use_nms, ", ".join(repr(k) for k in L.NMS_KINDS)))
+        if self.use_nms != 'none':
+            if not 0.0 <= self.nms_thresh < 1.0:
+                raise ValueError("TEST.NMS_THRESH %r with TEST.USE_NMS %r: the IoU threshold must be in [0, 1) (the default -1 means "
+                                 "\"not set\")" % (cfg.TEST.NMS_THRESH, self.use_nms))
+            if self.max_detection > L.NMS_MAX_ROWS:
+                raise NotImplementedError("TEST.USE_NMS %r with TEST.DETECTIONS_PER_IMG %d: the suppression kernel keeps one image's pair matrix "
+                                          "and ranking in one workgroup's LDS, at most %d rows" % (self.use_nms, self.max_detection, L.NMS_MAX_ROWS))
 
     @staticmethod
     def prepare_targets(targets, device):
@@ -81,9 +95,21 @@ class PostProcessor(nn.Module):
 
     def decode_device(self, hm, pad, calib, size, cls_planar=None, return_unc=False):
         """hm fp32 (B,H,W,64) -> det (B,K,14), topk (B,K,5) [score, flat index, cls, y, x], valid (B,K) int32
-        [, unc (B,K,2) = estimated_depth_error, uncertainty_conf]."""
+        [, unc (B,K,2) = estimated_depth_error, uncertainty_conf].  Under TEST.USE_NMS '2d' / '3d' valid is the mask after the suppression
+        (one more launch, ops.box_nms); det and topk are what they are without it."""
         if self.output_depth == 'oracle':
             raise ValueError("output_depth = 'oracle' reads the ground truth of each image: call the module (forward) with the dataset's targets")
+        out = self._decode(hm, pad, calib, size, cls_planar, return_unc)
+        if self.use_nms == 'none':
+            return out
+        return tuple(out[:2]) + (self.suppress(out[0], out[2]),) + tuple(out[3:])
+
+    def suppress(self, det, valid):
+        """valid (B,K) after TEST.USE_NMS '2d' / '3d' on the rows det (B,K,14): ops.box_nms, one launch, no host synchronisation."""
+        return ops.box_nms(det, valid, self.use_nms, self.nms_thresh, self.nms_class_agnostic)
+
+    def _decode(self, hm, pad, calib, size, cls_planar, return_unc):
+        """The decode alone: top-K and box rows, valid = score >= threshold."""
         scores, index = ops.decode_topk(hm, 0, self.num_classes, self.max_detection, planar=cls_planar)
         # (`output_depth` is read at every call: engine/inference.py:166 re-assigns it between the passes of `eval_all_depths`)
         self.head_set.check_output_depth(self.output_depth)
@@ -128,7 +154,12 @@ class PostProcessor(nn.Module):
         if self.output_depth == 'oracle':
             det, topk, valid, unc = self.decode_oracle(hm, pad, calib, size, predictions.get('cls_planar'), targets)
         else:
-            det, topk, valid, unc = self.decode_device(hm, pad, calib, size, predictions.get('cls_planar'), return_unc=True)
+            det, topk, valid, unc = self._decode(hm, pad, calib, size, predictions.get('cls_planar'), True)
+        # TEST.USE_NMS: on the rows the decode (under 'oracle': the per-detection choice of row) produced; everything below follows the mask
+        # after it, and 'valid_pre_nms' carries the decode's own
+        valid_pre = None
+        if self.use_nms != 'none':
+            valid_pre, valid = valid, self.suppress(det, valid)
         keep = valid.bool()
         results = [det[b][keep[b]] for b in range(det.shape[0])]          # host sync, as detector_infer.py:106
         vis_scores = [topk[b][keep[b], 0] for b in range(det.shape[0])]
@@ -139,7 +170,7 @@ class PostProcessor(nn.Module):
         depth_error = one([unc[b][keep[b], 0] for b in range(det.shape[0])]) if report else None
         unc_conf = one([unc[b][keep[b], 1] for b in range(det.shape[0])]) if report else None
         eval_utils = {'dis_ious': dis_ious, 'depth_errors': depth_errors, 'vis_scores': one(vis_scores), 'uncertainty_conf': unc_conf,
-                      'estimated_depth_error': depth_error, 'topk': topk, 'valid': valid, 'det_all': det}
+                      'estimated_depth_error': depth_error, 'topk': topk, 'valid': valid, 'det_all': det, 'valid_pre_nms': valid_pre}
         visualize_preds = {'heat_map': predictions['cls']}
         result = results[0] if len(results) == 1 else results
         return result, eval_utils, visualize_preds

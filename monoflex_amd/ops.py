@@ -618,6 +618,90 @@ def box3d_iou(a, b):
     return out
 
 
+@on_tensor_device
+def box_nms(det, valid, kind, thresh, class_agnostic=False):
+    """Greedy suppression of duplicate detections per image (mfx_box_nms; TEST.USE_NMS '2d' / '3d', which the reference declares and never
+    reads: the semantics are in INTEGRATION.md).  det (B, K, 14) fp32 rows of decode_boxes, valid (B, K) int32, kind '2d' | '3d',
+    thresh in [0, 1) -> valid_out (B, K) int32 = valid & kept; det is not touched.  Rows are ranked by score (column 13) descending, ties to
+    the lower slot; a row is kept unless an already kept row (of its class, unless class_agnostic) overlaps it with IoU > thresh.
+    CUDA tensors: one launch on the current stream, no host synchronisation, K <= 128.  CPU tensors: a float64 restatement on the host."""
+    if kind not in L.NMS_KINDS:
+        raise ValueError("box_nms: kind %r is not one of %s" % (kind, sorted(L.NMS_KINDS)))
+    if not 0.0 <= float(thresh) < 1.0:
+        raise ValueError("box_nms: thresh %r is outside [0, 1)" % (thresh,))
+    if det.dim() != 3 or det.shape[2] != 14 or tuple(valid.shape) != tuple(det.shape[:2]):
+        raise RuntimeError("box_nms: det (B, K, 14) and valid (B, K), got %s and %s" % (tuple(det.shape), tuple(valid.shape)))
+    if det.dtype != torch.float32 or valid.dtype != torch.int32:
+        raise TypeError("box_nms: det is float32 and valid is int32")
+    if not det.is_cuda and not valid.is_cuda:
+        return _box_nms_host(det, valid, kind, float(thresh), bool(class_agnostic))
+    _need_cuda(det, valid)
+    B, K = valid.shape
+    x, v = det.detach().contiguous(), valid.contiguous()
+    out = torch.empty_like(v)
+    L.check(L.load().mfx_box_nms(_ptr(x), _ptr(v), B, K, L.NMS_KINDS[kind], ctypes.c_float(float(thresh)), int(bool(class_agnostic)), _ptr(out),
+                                 _stream()), "mfx_box_nms")
+    return out
+
+
+def _box_nms_host(det, valid, kind, thresh, class_agnostic):
+    """box_nms on CPU tensors: the pairwise IoU matrix of an image in float64 (2D: vectorised; 3D: the host form of get_iou_3d on corner
+    tables, kept in float64), the ranking by a stable sort, the walk over it."""
+    import numpy as np
+    from .model.layers.iou_loss import _iou_3d_host
+    B, K = valid.shape
+    d = det.detach().double()
+    out = torch.zeros_like(valid)
+    for b in range(B):
+        idx = torch.nonzero(valid[b] != 0).flatten()
+        n = idx.numel()
+        if n == 0:
+            continue
+        r = d[b, idx]
+        if kind == '2d':
+            x1, y1, x2, y2 = (r[:, c] for c in (2, 3, 4, 5))
+            iw = (torch.minimum(x2[:, None], x2[None]) - torch.maximum(x1[:, None], x1[None])).clamp(min=0)
+            ih = (torch.minimum(y2[:, None], y2[None]) - torch.maximum(y1[:, None], y1[None])).clamp(min=0)
+            area = (x2 - x1) * (y2 - y1)
+            iou = iw * ih / (area[:, None] + area[None] - iw * ih)                       # 0 / 0 = NaN: not > thresh
+        else:
+            i, j = torch.triu_indices(n, n, 1)
+            # only pairs that can meet are evaluated: rectangles whose circumscribed circles do not touch share no area (IoU 0)
+            reach = 0.5 * torch.hypot(r[:, 8], r[:, 7])
+            can = torch.hypot(r[i, 9] - r[j, 9], r[i, 11] - r[j, 11]) <= reach[i] + reach[j]
+            can |= ~torch.isfinite(r[i].sum(1) + r[j].sum(1))
+            if not class_agnostic:
+                can &= r[i, 0] == r[j, 0]
+            i, j = i[can], j[can]
+            iou = torch.zeros((n, n), dtype=torch.float64)
+            if i.numel():
+                corners = _corner_tables(r)
+                iou[i, j] = torch.from_numpy(_iou_3d_host(corners[i].numpy(), corners[j].numpy()))
+                iou = iou + iou.T
+        over = (iou > thresh).numpy()
+        if not class_agnostic:
+            over &= (r[:, 0][:, None] == r[:, 0][None]).numpy()
+        score = r[:, 13].numpy()
+        order = np.argsort(-np.where(np.isnan(score), -np.inf, score), kind="stable")    # ties: the lower slot (idx ascends)
+        kept = np.zeros(n, dtype=bool)
+        for c in order:
+            if not (over[c] & kept).any():
+                kept[c] = True
+        out[b, idx[torch.from_numpy(kept)]] = 1
+    return out
+
+
+def _corner_tables(rows):
+    """det rows (n, 14) float64 -> (n, 8, 3) corner tables in encode_box3d order of the boxes (x, y - h / 2, z, l, h, w, ry)."""
+    sx = rows.new_tensor([-1, -1, 1, 1, -1, -1, 1, 1]) * 0.5
+    sy = rows.new_tensor([1, 1, 1, 1, -1, -1, -1, -1]) * 0.5
+    sz = rows.new_tensor([-1, 1, 1, -1, -1, 1, 1, -1]) * 0.5
+    h, w, l, x, y, z, ry = (rows[:, c:c + 1] for c in (6, 7, 8, 9, 10, 11, 12))
+    c, s = torch.cos(ry), torch.sin(ry)
+    px, py, pz = l * sx, h * sy, w * sz
+    return torch.stack((c * px + s * pz + x, py + (y - h / 2), -s * px + c * pz + z), dim=2)
+
+
 # ---- validation diagnostics at the ground-truth centres (TEST.EVAL_DEPTH / TEST.EVAL_DIS_IOUS) ------------------------------------------
 EVAL_DEPTH_KEYS = ("direct", "direct_sigma", "keypoint_center", "keypoint_02", "keypoint_13", "keypoint_center_sigma", "keypoint_02_sigma",
                    "keypoint_13_sigma", "sigma_min", "sigma_weighted", "mean", "min", "target")       # detector_infer.py:341-357, mfx_eval_diagnostics' columns
