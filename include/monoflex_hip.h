@@ -83,7 +83,8 @@ int mfx_commit_options(void);
  *   DCN backward: "dcn_bt_tile" (dcn_bwd_tile_kernel), "dcn_bt_sample" (dcn_bwd_sample_kernel), "dcn_bt_far" (far-corner kernels, both forms);
  *   "gram" (mfx_gram_heads phase calls), "adamw_multi" (one-launch AdamW), "optim_multi" (mfx_optim_multi: the one-launch update with a rule
  *   and / or a gradient coefficient), "grad_norm_multi" (mfx_grad_norm_multi: the gradient norm of the clipped update).
- * Post-processing: "box_nms" (launches of mfx_box_nms: one per call that had rows, whatever B).
+ * Post-processing: "box_nms" (launches of mfx_box_nms: one per call that had rows, whatever B), "decode_multi" (launches of
+ *   mfx_decode_boxes_multi: one per call with B > 0; the default inference path never takes it).
  * Unknown names return MFX_ERR_ARG (negative). */
 long mfx_get_counter(const char* name);
 
@@ -415,6 +416,27 @@ int mfx_decode_boxes_heads(const float* hmap, int ld, int reg_off, const float* 
                            int ncls, int B, int H, int W, int K, const float* calib, const int32_t* pad,
                            const int32_t* img_size, float threshold, const mfx_decode_cfg* cfg, const mfx_head_layout* heads,
                            float* det, float* topk, int32_t* valid, float* unc, void* stream);
+/* Any subset of the eight depth modes AND the reference's 'oracle' (detector_infer.py:199-202, get_oracle_depths :239-278) from ONE launch:
+ * the 2D box, dimensions, alpha and the four depth estimates of a detection are computed once, then the rows of every requested mode are
+ * finished from them.  `modes`: bit m = MFX_DEPTH_* value m, bit MFX_DEPTH_ORACLE = 'oracle'; NM = popcount(modes) slices per image in
+ * ascending bit order.  Slice i of det / unc is bit for bit what mfx_decode_boxes_heads writes with cfg->output_depth = that mode
+ * (cfg->output_depth itself is not read here); topk / valid are those of mfx_decode_boxes_heads.
+ * 'oracle' matches every detection with score >= threshold against its image's ground-truth table on the device
+ * (csrc/decode_oracle_math.h is the rule): gt_rows fp32 [B][M][8] = reg_mask, cls_id, x1, y1, x2, y2, depth, 0; slots with reg_mask != 0
+ * take part, in slot order; image b reads table b.  The nearest object by squared box-centre distance -- replaced by the literal 9999 where
+ * the classes differ --, first minimum; matched unless the 2D IoU < 0.5 (0 / 0 = NaN counts as matched); the matched detection takes the
+ * row of the single-estimate mode (direct -- only with depth_uncertainty --, keypoints_center, _02, _13) whose depth is closest to the
+ * object's, first minimum; everything else keeps the MFX_DEPTH_MEAN row.  The oracle bit needs corner_uncertainty (as 'mean' does) and
+ * gt_rows with 1 <= M <= 128.
+ * oracle_choice: optional int32 [B][K], -1 = kept the mean, else the column 0..3 (0 = direct); written only with the oracle bit.
+ * unc: optional fp32 [B][NM][K][2].  One launch of B workgroups (counter "decode_multi"), no allocation, no synchronisation,
+ * hipGraph-capturable.  A refused argument is MFX_ERR_ARG with the reason in mfx_last_error(), and nothing is launched. */
+enum { MFX_DEPTH_ORACLE = 8 };
+int mfx_decode_boxes_multi(const float* hmap, int ld, int reg_off, const float* scores, const int32_t* index,
+                           int ncls, int B, int H, int W, int K, const float* calib, const int32_t* pad,
+                           const int32_t* img_size, float threshold, const mfx_decode_cfg* cfg, const mfx_head_layout* heads,
+                           uint32_t modes, const float* gt_rows, int M, float* det, float* topk, int32_t* valid, float* unc,
+                           int32_t* oracle_choice, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (3) training path (reference: autograd over nn.Conv2d / BatchNorm2d / MaxPool2d / ConvTranspose2d and

@@ -210,5 +210,36 @@ MFX_HD Row decode_row(const float* r, float px, float py, int cls, float score, 
     return o;
 }
 
+// ---- decode_row in two parts (decode_multi.hip: several depth modes of one detection) -------------------------------------------------------
+// What no depth mode changes: the 2D box, the dimensions (l, h, w), the local angle before any wrap, the 3D offset and the four estimates.
+// finish_row(shared_part(...), ..., combine(estimates, mode, ...)) is decode_row under that mode, expression for expression.
+struct Shared { float box[4], dims[3], alpha, offx, offy; Estimates e; };
+
+MFX_HD void shared_part(const float* r, float px, float py, int cls, const Camera& c, float wmax, float hmax, const mfx_decode_cfg& dc,
+                        const mfx_head_layout& hl, Shared& s) {
+    decode_box2d(r, hl, px, py, c, dc.down_ratio, wmax, hmax, s.box);
+    decode_dims(r, dc, hl, cls, s.dims);
+    decode_estimates(r, dc, hl, c.fu, s.dims[1], s.e);
+    s.offx = r[hl.ch[HK_OFF3D]]; s.offy = r[hl.ch[HK_OFF3D] + 1];
+    s.alpha = decode_alpha(r, hl);
+}
+
+// the row from a depth, its sigma and has_err (a Combined)
+MFX_HD Row finish_row(const Shared& s, float px, float py, int cls, float score, const Camera& c, const mfx_decode_cfg& dc, const Combined& z) {
+    Row o;
+    float loc[3];
+    decode_location(px, py, s.offx, s.offy, z.depth, c, dc.down_ratio, loc);
+    o.det[0] = (float)cls; o.det[1] = wrap_pi(s.alpha);
+    for (int i = 0; i < 4; ++i) o.det[2 + i] = s.box[i];
+    o.det[6] = s.dims[1]; o.det[7] = s.dims[2]; o.det[8] = s.dims[0];
+    o.det[9] = loc[0]; o.det[10] = loc[1] + s.dims[1] / 2.f; o.det[11] = loc[2];
+    o.det[12] = roty_of(s.alpha, loc[0], loc[2]);
+    o.sigma = z.sigma;
+    o.conf = 1.f - clampf(z.sigma, 0.01f, 1.f);
+    o.as_conf = dc.uncertainty_as_conf && z.has_err;
+    o.det[13] = o.as_conf ? score * o.conf : score;
+    return o;
+}
+
 }  // namespace bdec
 }  // namespace mfx

@@ -109,6 +109,7 @@
     X(conv_bn_stats, "convolutions whose epilogue accumulated the BatchNorm statistics") \
     X(edge_chain, "launches of the edge fusion's one-kernel conv chain (edge_chain.hip)") \
     X(box_nms, "launches of the duplicate suppression (box_nms.hip): one per mfx_box_nms call that had rows, whatever B") \
+    X(decode_multi, "launches of the several-modes-and-oracle box decode (decode_multi.hip): one per mfx_decode_boxes_multi call with B > 0") \
     /* training-side families */ \
     X(wgrad_patch, "weight gradients by the LDS-patch kernel (wgrad_tr.hip)") \
     X(wgrad_tr, "weight gradients by the transposed-read kernel (wgrad_tr.hip)") \

@@ -38,33 +38,57 @@ class _DiagnosticSums:
         out["objects"] = n
 
 
-def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, overlap=True, diagnostics=None):
+def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, overlap=True, diagnostics=None, methods=None, folders=None):
     """Returns the number of images processed; `timer`, if given, is a dict that receives the seconds spent in the model (launches + waits).
     `overlap` (default, CUDA only): ONE batch stays in flight -- the fixed-size (B,50,14) rows and validity flags of batch k are copied to
     pinned memory behind an event, batch k+1 is launched, and only then does the host wait for batch k's event and write its files
     (the reference's loop, engine/inference.py:26-56, waits for every batch before it touches the next: 21 % of the time at B = 8, bench.py
-    `pipeline` leg).  Same rows, same files: the per-image selection `det[b][valid[b]]` is the one PostProcessor.forward makes."""
+    `pipeline` leg).  Same rows, same files: the per-image selection `det[b][valid[b]]` is the one PostProcessor.forward makes.
+    OUTPUT_DEPTH 'oracle' keeps the overlap: its ground-truth table (ops.oracle_gt_rows, from the loader's stacked `fields` or the targets)
+    goes to the device with the batch and the match runs there; targets without labels raise ValueError.
+    `methods` + `folders` (equally long; `predict_folder` is then not used): ONE walk of the loader writes the result files of every depth
+    method of `methods` into its folder of `folders` -- one network pass and one (B,NM,50,14) copy per batch (KeypointDetector.detect_all_device),
+    the files being those of a walk per method with `post_processor.output_depth` set to it.  This form needs the device path (a CUDA device)
+    and computes no diagnostics."""
     model.eval()
     n, busy = 0, 0.0
     dev = torch.device(device)
     overlap = bool(overlap) and dev.type == "cuda" and hasattr(model, "detect_device")
-    if getattr(getattr(getattr(model, "heads", None), "post_processor", None), "output_depth", None) == "oracle":
-        overlap = False                                            # reads each image's ground truth on the host (PostProcessor.decode_oracle)
     pending = None
     post = getattr(getattr(model, "heads", None), "post_processor", None)
     want = int(getattr(post, "diagnostics_wanted", 0))
     sums = _DiagnosticSums()
+    multi = methods is not None
+    if multi:
+        methods, folders = list(methods), list(folders if folders is not None else ())
+        if len(methods) != len(folders) or not methods:
+            raise ValueError("compute_on_dataset: `methods` and `folders` pair up (one result folder per depth method)")
+        if not (dev.type == "cuda" and hasattr(model, "detect_all_device")):
+            raise RuntimeError("compute_on_dataset: the one-pass form over several depth methods runs on the device path (CUDA)")
+        overlap, want = bool(overlap), 0
+    oracle = 'oracle' in methods if multi else getattr(post, "output_depth", None) == "oracle"
 
     def pinned(t):
         h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
         h.copy_(t, non_blocking=True)
         return h
 
+    def labelled_source(batch, targets):
+        """What the ground-truth tables are stacked from: the loader's batch-stacked `fields` when the targets carry labels, else the targets
+        (the test split's carry none: ValueError from the table builders, as forward)."""
+        fields = batch.get("fields")
+        labelled = fields is not None and all(t.has_field("reg_mask") for t in targets)
+        return fields if labelled else targets
+
     def finish(p):
         ev, rows_h, valid_h, ids, diag_h = p
         ev.synchronize()
         for b, image_id in enumerate(ids):
-            generate_kitti_3d_detection(rows_h[b][valid_h[b].bool()], os.path.join(predict_folder, image_id + ".txt"))
+            if multi:
+                for i, folder in enumerate(folders):
+                    generate_kitti_3d_detection(rows_h[b, i][valid_h[b, i].bool()], os.path.join(folder, image_id + ".txt"))
+            else:
+                generate_kitti_3d_detection(rows_h[b][valid_h[b].bool()], os.path.join(predict_folder, image_id + ".txt"))
         if diag_h is not None:
             sums.add(*diag_h)
         return len(ids)
@@ -75,10 +99,14 @@ def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, o
             images = images.to(device)
             targets = [t.to(device) for t in targets]
             t0 = time.perf_counter()
-            if overlap:
+            if overlap or multi:
                 tensors = images.tensors if hasattr(images, "tensors") else images
                 dt = model.device_targets(targets, dev)
-                det, _, valid, hm = model.detect_device(tensors, *dt)
+                gt = ops.oracle_gt_rows(labelled_source(batch, targets), dev) if oracle else None
+                if multi:
+                    det, _, valid, hm = model.detect_all_device(tensors, *dt, methods=methods, gt_rows=gt)
+                else:
+                    det, _, valid, hm = model.detect_device(tensors, *dt, gt_rows=gt)
                 rows_h = torch.empty(det.shape, dtype=det.dtype, pin_memory=True)
                 valid_h = torch.empty(valid.shape, dtype=valid.dtype, pin_memory=True)
                 rows_h.copy_(det, non_blocking=True)
@@ -86,9 +114,7 @@ def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, o
                 diag_h = None
                 if want:        # the diagnostics kernel, the ~16 small torch launches that stack its (B,M,16) table (a fill, casts, slice copies) and up to
                                 # three more fixed-shape copies to pinned memory, all behind the same event: no synchronisation is added
-                    fields = batch.get("fields")                       # (the test split's targets carry no labels: ValueError, as forward)
-                    labelled = fields is not None and all(t.has_field("reg_mask") for t in targets)
-                    gt_rows = ops.eval_diag_rows(fields if labelled else targets, dev)
+                    gt_rows = ops.eval_diag_rows(labelled_source(batch, targets), dev)
                     depth_err, iou = model.diagnose_device(hm, gt_rows, dt[2], dt[3])
                     diag_h = (None if depth_err is None else pinned(depth_err), None if iou is None else pinned(iou),
                               pinned(gt_rows[..., 0].contiguous()))
@@ -98,6 +124,12 @@ def compute_on_dataset(model, data_loader, device, predict_folder, timer=None, o
                 if pending is not None:
                     n += finish(pending)
                 pending = (ev, rows_h, valid_h, list(image_ids), diag_h)
+                if not overlap:                                        # (the one-pass form without the overlap: wait for this batch now)
+                    t0 = time.perf_counter()
+                    ev.synchronize()
+                    busy += time.perf_counter() - t0
+                    n += finish(pending)
+                    pending = None
                 continue
             output, eval_utils, _ = model(images, targets)
             outputs = [output] if torch.is_tensor(output) else list(output)
@@ -161,11 +193,16 @@ def inference(model, data_loader, dataset_name, eval_types=("detections",), devi
 EVAL_DEPTH_METHODS = ("oracle", "hard", "soft", "mean", "direct", "keypoints_center", "keypoints_02", "keypoints_13")   # engine/inference.py:154
 
 
-def inference_all_depths(model, data_loader, dataset_name, eval_types=("detections",), device="cuda", output_folder=None, metrics=("R40",)):
-    """`--eval_all_depths` (engine/inference.py:131-198): the evaluation once per depth-solving method, each into
-    `<output_folder>/eval_all_depths/<method>`, by re-assigning `post_processor.output_depth` between passes (the decode kernel reads the mode
-    per launch; 'oracle' needs the ground-truth fields of a validation split).  Logs the Car AP@0.70 bev/3d line per method and the ranking by
-    3D moderate.  A reduced head set walks the methods it can serve.  -> {method: ret_dict} on rank 0 (the reference returns (None, None, None); the log lines are its product), the attribute restored."""
+def inference_all_depths(model, data_loader, dataset_name, eval_types=("detections",), device="cuda", output_folder=None, metrics=("R40",),
+                         single_pass=True):
+    """`--eval_all_depths` (engine/inference.py:131-198): the evaluation under every depth-solving method, each into
+    `<output_folder>/eval_all_depths/<method>` ('oracle' needs the ground-truth fields of a validation split).  Logs the Car AP@0.70 bev/3d
+    line per method and the ranking by 3D moderate.  A reduced head set walks the methods it can serve.
+    `single_pass` (default): ONE walk of the loader -- every image is read and runs through the network once, and one decode launch emits the
+    rows of all the methods (compute_on_dataset's `methods` form; the method enters a row through the location, roty, the score and nothing
+    else).  False: the reference's loop, one whole pass per method, by re-assigning `post_processor.output_depth` between passes.  Same
+    folders, byte-identical files, same log lines, same return value.
+    -> {method: ret_dict} on rank 0 (the reference returns (None, None, None); the log lines are its product), the attribute restored."""
     import numpy as np
     import torch.distributed as dist
     logger = logging.getLogger("monoflex.inference")
@@ -175,23 +212,40 @@ def inference_all_depths(model, data_loader, dataset_name, eval_types=("detectio
     root = os.path.join(output_folder, "eval_all_depths")
     rank0 = not (dist.is_available() and dist.is_initialized() and dist.get_rank() != 0)
     ret = {}
+
+    def prepare(method):
+        logger.info("evaluation with depth method: %s", method)
+        folder = os.path.join(root, method)
+        os.makedirs(folder, exist_ok=True)
+        if rank0:
+            for f in os.listdir(folder):                               # stale predictions of an earlier run (:162-164)
+                os.remove(os.path.join(folder, f))
+        return folder
+
+    def evaluate(method, folder):
+        _, ret[method] = evaluate_python(label_path=dataset.label_dir, result_path=folder, label_split_file=dataset.imageset_txt,
+                                         current_class=dataset.classes, metric="R40", device=device)
+
     try:
         # (a reduced head set serves a subset: lib.HeadSet.output_depths -- the others would raise in the reference, and are refused here)
         methods = [m for m in EVAL_DEPTH_METHODS if m in post.head_set.output_depths()]
-        for method in methods:
-            logger.info("evaluation with depth method: %s", method)
-            folder = os.path.join(root, method)
-            os.makedirs(folder, exist_ok=True)
-            if rank0:
-                for f in os.listdir(folder):                               # stale predictions of an earlier run (:162-164)
-                    os.remove(os.path.join(folder, f))
+        if single_pass:
+            folders = [prepare(m) for m in methods]
             barrier()
-            post.output_depth = method
-            compute_on_dataset(model, data_loader, torch.device(device), folder)
+            compute_on_dataset(model, data_loader, torch.device(device), None, methods=methods, folders=folders)
             barrier()
             if rank0:
-                _, ret[method] = evaluate_python(label_path=dataset.label_dir, result_path=folder, label_split_file=dataset.imageset_txt,
-                                                 current_class=dataset.classes, metric="R40", device=device)
+                for method, folder in zip(methods, folders):
+                    evaluate(method, folder)
+        else:
+            for method in methods:
+                folder = prepare(method)
+                barrier()
+                post.output_depth = method
+                compute_on_dataset(model, data_loader, torch.device(device), folder)
+                barrier()
+                if rank0:
+                    evaluate(method, folder)
     finally:
         post.output_depth = before
     if not rank0:

@@ -246,10 +246,13 @@ SYMBOLS = {
     "mfx_decode_boxes_cfg": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.POINTER(DecodeCfg), _P, _P, _P, _P, _P]),
     "mfx_decode_boxes_heads": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.POINTER(DecodeCfg), ctypes.POINTER(HeadLayout),
                                     _P, _P, _P, _P, _P]),
+    "mfx_decode_boxes_multi": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.POINTER(DecodeCfg), ctypes.POINTER(HeadLayout),
+                                    ctypes.c_uint32, _P, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 # mfx_decode_boxes_mode's depth_mode (include/monoflex_hip.h MFX_DEPTH_*), by the reference's `output_depth` names (detector_infer.py:149-198)
 DEPTH_MODES = {"soft": 0, "hard": 1, "mean": 2, "direct": 3, "keypoints_avg": 4, "keypoints_center": 5, "keypoints_02": 6, "keypoints_13": 7}
+DEPTH_ORACLE = 8                                                # MFX_DEPTH_ORACLE: the bit of 'oracle' in mfx_decode_boxes_multi's `modes` (no decode mode of its own)
 
 NMS_KINDS = {"2d": 1, "3d": 2}                                  # mfx_box_nms' `kind` (MFX_NMS_2D / MFX_NMS_3D) by TEST.USE_NMS value; 'none' launches nothing
 NMS_MAX_ROWS = 128                                              # its K limit

@@ -49,10 +49,20 @@ class KeypointDetector(nn.Module):
         return super().train(mode)
 
     # ---- device pipeline: no host sync, static shapes ------------------------------------------------
-    def detect_device(self, images, edge_indices, edge_lens, pad, calib, size, edge_rowmap=None):
+    def detect_device(self, images, edge_indices, edge_lens, pad, calib, size, edge_rowmap=None, gt_rows=None):
+        """`gt_rows` (ops.oracle_gt_rows): the ground-truth table OUTPUT_DEPTH 'oracle' matches against on the device; not read otherwise."""
         feat = self.backbone.forward_nhwc(images)
         hm = self.heads.predictor.forward_nhwc(feat, edge_indices, edge_lens, edge_rowmap)
-        det, topk, valid = self.heads.post_processor.decode_device(hm, pad, calib, size, self.heads.predictor.last_cls_planar)
+        det, topk, valid = self.heads.post_processor.decode_device(hm, pad, calib, size, self.heads.predictor.last_cls_planar, gt_rows=gt_rows)
+        return det, topk, valid, hm
+
+    def detect_all_device(self, images, edge_indices, edge_lens, pad, calib, size, edge_rowmap, methods, gt_rows=None):
+        """One network pass, the rows of every depth method of `methods` ('oracle' included, with `gt_rows`):
+        (det (B,NM,K,14), topk (B,K,5), valid (B,NM,K), hm) -- PostProcessor.decode_all_device on this batch's maps."""
+        feat = self.backbone.forward_nhwc(images)
+        hm = self.heads.predictor.forward_nhwc(feat, edge_indices, edge_lens, edge_rowmap)
+        det, topk, valid, _ = self.heads.post_processor.decode_all_device(hm, pad, calib, size, self.heads.predictor.last_cls_planar, methods,
+                                                                          gt_rows=gt_rows)
         return det, topk, valid, hm
 
     def diagnose_device(self, hm, gt_rows, pad, calib):

@@ -93,16 +93,49 @@ class PostProcessor(nn.Module):
         size = torch.tensor(list(targets[0].size), dtype=torch.int32, device=device)
         return pad.contiguous(), calib.contiguous(), size
 
-    def decode_device(self, hm, pad, calib, size, cls_planar=None, return_unc=False):
+    def decode_device(self, hm, pad, calib, size, cls_planar=None, return_unc=False, gt_rows=None):
         """hm fp32 (B,H,W,64) -> det (B,K,14), topk (B,K,5) [score, flat index, cls, y, x], valid (B,K) int32
         [, unc (B,K,2) = estimated_depth_error, uncertainty_conf].  Under TEST.USE_NMS '2d' / '3d' valid is the mask after the suppression
-        (one more launch, ops.box_nms); det and topk are what they are without it."""
+        (one more launch, ops.box_nms); det and topk are what they are without it.  `gt_rows` (B,M,8) (ops.oracle_gt_rows): the ground truth
+        output_depth 'oracle' matches against on the device (one ops.decode_boxes_multi launch); 'oracle' without it is refused."""
         if self.output_depth == 'oracle':
-            raise ValueError("output_depth = 'oracle' reads the ground truth of each image: call the module (forward) with the dataset's targets")
-        out = self._decode(hm, pad, calib, size, cls_planar, return_unc)
+            if gt_rows is None:
+                raise ValueError("output_depth = 'oracle' reads the ground truth of each image: pass gt_rows (ops.oracle_gt_rows), or call the "
+                                 "module (forward) with the dataset's targets")
+            out = self._decode_oracle_device(hm, pad, calib, size, cls_planar, gt_rows)
+            out = out if return_unc else out[:3]
+        else:
+            out = self._decode(hm, pad, calib, size, cls_planar, return_unc)
         if self.use_nms == 'none':
             return out
         return tuple(out[:2]) + (self.suppress(out[0], out[2]),) + tuple(out[3:])
+
+    def _decode_oracle_device(self, hm, pad, calib, size, cls_planar, gt_rows):
+        """`output_depth = 'oracle'` on the device: (det, topk, valid, unc), what decode_oracle assembles on the host."""
+        self.head_set.check_output_depth('oracle')
+        scores, index = ops.decode_topk(hm, 0, self.num_classes, self.max_detection, planar=cls_planar)
+        det, topk, valid, unc, _ = ops.decode_boxes_multi(hm, REG_OFF, scores, index, calib, pad, size, float(self.det_threshold), ('oracle',),
+                                                          self.decode_cfg, heads=self.head_layout, gt_rows=gt_rows, return_unc=True)
+        return det[:, 0], topk, valid, unc[:, 0]
+
+    def decode_all_device(self, hm, pad, calib, size, cls_planar, methods, gt_rows=None, return_unc=False):
+        """The rows of every depth method of `methods` (names of head_set.output_depths(), 'oracle' with `gt_rows`) from one top-K and one
+        ops.decode_boxes_multi launch: det (B,NM,K,14), topk (B,K,5), valid (B,NM,K) int32, unc (B,NM,K,2) or None; slice i is what
+        decode_device gives under output_depth = methods[i].  Under TEST.USE_NMS valid is the mask after ONE ops.box_nms launch on the
+        (B * NM, K, 14) view; without it the decode's mask repeated."""
+        methods = list(methods)
+        for m in methods:
+            self.head_set.check_output_depth(m)
+        if 'oracle' in methods and gt_rows is None:
+            raise ValueError("output_depth = 'oracle' reads the ground truth of each image: pass gt_rows (ops.oracle_gt_rows)")
+        scores, index = ops.decode_topk(hm, 0, self.num_classes, self.max_detection, planar=cls_planar)
+        det, topk, valid, unc, _ = ops.decode_boxes_multi(hm, REG_OFF, scores, index, calib, pad, size, float(self.det_threshold), methods,
+                                                          self.decode_cfg, heads=self.head_layout, gt_rows=gt_rows, return_unc=return_unc)
+        B, NM, K = det.shape[:3]
+        valid = valid[:, None, :].expand(B, NM, K).contiguous()
+        if self.use_nms != 'none':
+            valid = self.suppress(det.reshape(B * NM, K, 14), valid.reshape(B * NM, K)).reshape(B, NM, K)
+        return det, topk, valid, unc
 
     def suppress(self, det, valid):
         """valid (B,K) after TEST.USE_NMS '2d' / '3d' on the rows det (B,K,14): ops.box_nms, one launch, no host synchronisation."""
@@ -151,8 +184,10 @@ class PostProcessor(nn.Module):
         if self.diagnostics_wanted:
             gt_rows = ops.eval_diag_rows(targets, hm.device)            # ValueError on targets without labels (the `test` split)
             depth_errors, dis_ious = self.diagnostics_tables(*self.diagnose_device(hm, gt_rows, pad, calib), gt_rows[..., 0])
-        if self.output_depth == 'oracle':
-            det, topk, valid, unc = self.decode_oracle(hm, pad, calib, size, predictions.get('cls_planar'), targets)
+        if self.output_depth == 'oracle':                                    # matched on the device; decode_oracle below is the host form of the rule
+            self.head_set.check_output_depth('oracle')
+            det, topk, valid, unc = self._decode_oracle_device(hm, pad, calib, size, predictions.get('cls_planar'),
+                                                               ops.oracle_gt_rows(targets, hm.device))
         else:
             det, topk, valid, unc = self._decode(hm, pad, calib, size, predictions.get('cls_planar'), True)
         # TEST.USE_NMS: on the rows the decode (under 'oracle': the per-detection choice of row) produced; everything below follows the mask

@@ -454,6 +454,86 @@ def decode_boxes(hmap, reg_off, scores, index, calib, pad, img_size, threshold, 
     return (det, topk, valid, unc) if return_unc else (det, topk, valid)
 
 
+ORACLE_GT_FIELDS = ("reg_mask", "cls_ids", "gt_bboxes", "locations")
+ORACLE_GT_ROW = 8
+
+
+def oracle_gt_rows(source, device):
+    """The ground-truth table OUTPUT_DEPTH 'oracle' matches against (mfx_decode_boxes_multi), fp32 (B, M, 8) on `device`: reg_mask, cls_id,
+    2D box x1, y1, x2, y2, depth (locations[..., 2]), one spare.  `source`: the loader's batch-stacked `fields` dict, or the per-image
+    ParamsLists (stacked here).  Targets without the ground-truth fields (the `test` split) raise ValueError."""
+    if isinstance(source, dict):
+        missing = [k for k in ORACLE_GT_FIELDS if k not in source]
+        get = lambda k: torch.as_tensor(source[k])
+    else:
+        source = list(source)
+        missing = [k for k in ORACLE_GT_FIELDS if not all(t.has_field(k) for t in source)]
+        get = lambda k: torch.stack([torch.as_tensor(t.get_field(k)) for t in source])
+    if missing:
+        raise ValueError("OUTPUT_DEPTH 'oracle' reads the ground truth of every image, and these targets have no %s "
+                         "(the `test` split has no labels: evaluate a split that has)" % ", ".join(missing))
+    mask = get("reg_mask")
+    B, M = mask.shape[:2]
+    f = lambda k, w: get(k).to(device=device, dtype=torch.float32).reshape(B, M, w)
+    rows = torch.zeros((B, M, ORACLE_GT_ROW), dtype=torch.float32, device=device)
+    rows[:, :, 0:1] = f("reg_mask", 1)
+    rows[:, :, 1:2] = f("cls_ids", 1)
+    rows[:, :, 2:6] = f("gt_bboxes", 4)
+    rows[:, :, 6] = f("locations", 3)[:, :, 2]
+    return rows
+
+
+@on_tensor_device
+def decode_boxes_multi(hmap, reg_off, scores, index, calib, pad, img_size, threshold, modes, cfg, heads=None, gt_rows=None, return_unc=False):
+    """Several depth modes of decode_boxes, and the reference's 'oracle', from ONE launch on one top-K (mfx_decode_boxes_multi).
+    `modes`: a sequence of distinct names from lib.DEPTH_MODES plus 'oracle'; `cfg`: a lib.DecodeCfg (its own output_depth is not read);
+    `heads`: a lib.HeadLayout, None = the nine-key layout of runs/monoflex.yaml; `gt_rows` (B, M, 8) fp32 (oracle_gt_rows): required with
+    'oracle', M <= 128.  -> (det (B, NM, K, 14), topk (B, K, 5), valid (B, K), unc (B, NM, K, 2) or None, choice (B, K) int32 or None):
+    slice i is `modes[i]`, bit for bit the row decode_boxes(depth_mode=modes[i]) writes; an oracle row is the row of the single-estimate mode
+    the detection took, or the 'mean' row; choice = -1 (kept the mean) or the column 0..3 (0 = direct), only with 'oracle'.
+    No host synchronisation."""
+    _need_cuda(hmap, scores, index, calib, pad, img_size, gt_rows)
+    modes = list(modes)
+    bad = [m for m in modes if m not in L.DEPTH_MODES and m != 'oracle']
+    if bad or len(set(modes)) != len(modes):
+        raise ValueError("decode_boxes_multi: modes %r must be distinct names of %s or 'oracle'" % (modes, sorted(L.DEPTH_MODES)))
+    if cfg is None:
+        raise ValueError("decode_boxes_multi: needs a cfg (lib.decode_cfg)")
+    if heads is None:
+        heads = L.HeadSet([L.HEAD_KEYS], [[L.HEAD_WIDTHS[k] for k in L.HEAD_KEYS]]).layout()
+    bit = lambda m: L.DEPTH_ORACLE if m == 'oracle' else L.DEPTH_MODES[m]
+    mask = 0
+    for m in modes:
+        mask |= 1 << bit(m)
+    B, H, W, ld = hmap.shape
+    ncls, K = scores.shape[1], scores.shape[2]
+    NM = len(modes)
+    oracle = 'oracle' in modes
+    M = 0
+    if gt_rows is not None:
+        if gt_rows.dtype != torch.float32 or gt_rows.dim() != 3 or gt_rows.shape[0] != B or gt_rows.shape[2] != ORACLE_GT_ROW or not gt_rows.is_contiguous():
+            raise RuntimeError("decode_boxes_multi: gt_rows is a contiguous float32 (B, M, 8) table (oracle_gt_rows), got %s %s"
+                               % (gt_rows.dtype, tuple(gt_rows.shape)))
+        M = gt_rows.shape[1]
+    dev = hmap.device
+    det = torch.empty((B, NM, K, 14), dtype=torch.float32, device=dev)
+    topk = torch.empty((B, K, 5), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, K), dtype=torch.int32, device=dev)
+    unc = torch.empty((B, NM, K, 2), dtype=torch.float32, device=dev) if return_unc else None
+    choice = torch.empty((B, K), dtype=torch.int32, device=dev) if oracle else None
+    L.check(L.load().mfx_decode_boxes_multi(_ptr(hmap), ld, reg_off, _ptr(scores), _ptr(index), ncls, B, H, W, K, _ptr(calib), _ptr(pad),
+                                            _ptr(img_size), ctypes.c_float(threshold), ctypes.byref(cfg), ctypes.byref(heads), mask,
+                                            _ptr(gt_rows) if oracle else None, M, _ptr(det), _ptr(topk), _ptr(valid), _ptr(unc), _ptr(choice),
+                                            _stream()), "mfx_decode_boxes_multi")
+    # the kernel writes the slices in ascending bit order: hand them back in the order asked for
+    order = sorted(range(NM), key=lambda i: bit(modes[i]))                 # order[s] = position in `modes` of slice s
+    if order != list(range(NM)):
+        where = {i: s for s, i in enumerate(order)}                        # where[i] = slice of modes[i]
+        pick = lambda t: torch.stack([t[:, where[i]] for i in range(NM)], dim=1)       # (one device copy, no index tensor from the host)
+        det, unc = pick(det), None if unc is None else pick(unc)
+    return det, topk, valid, unc, choice
+
+
 # ---- reference `_ext` boundary (NCHW fp32) ---------------------------------------------------------
 _ws_cache = {}
 
