@@ -504,11 +504,13 @@ def _conv_backward(x, weight, dy, stride, pad, has_bias, Cout, needs, res=None):
             g = torch.empty((B, H, W, Cp), dtype=dy.dtype, device=dy.device)
             L.check(L.load().mfx_zero_insert2_nhwc(_ptr(dy), _ptr(g), B, Ho, Wo, Cp, H, W, _dt(dy.dtype), _stream()),
                     "mfx_zero_insert2_nhwc")
-        dx = ops.conv2d(g, pt, res=res if (res is not None and cin_pad == Cin) else None)
+        if res is not None and cin_pad != Cin:
+            # padded operand rows: the residual is padded alike and still added in the epilogue, in fp32 before the one rounding of dx
+            # (added to the sliced 16-bit dx afterwards it rounded twice: 9..73 entries per map off by one bf16 ulp at Cin = 20)
+            res = torch.nn.functional.pad(res, (0, cin_pad - Cin))
+        dx = ops.conv2d(g, pt, res=res)
         if cin_pad != Cin:
             dx = dx[..., :Cin]
-            if res is not None:
-                dx = dx + res
     need_w, need_b = bool(needs[1]), bool(has_bias and needs[2])
     if need_w or need_b:
         def leaves():                                           # the parameter gradients: leaves of the backward graph (see on_wgrad_stream)

@@ -1294,8 +1294,17 @@ def test_dcn_fused_sample_wgrad_kernel_vs_oracle(H, W, off_std, min_chunks, half
 def test_conv_wgrad_transposed_read_kernel_vs_torch(cin, cout, k, stride, H, W, half):
     """Second-generation weight-gradient kernel (wgrad_tr.hip: natural-layout LDS tiles + ds_read_b64_tr_b16, 64x64 wave
     blocks, BK = 192) against torch autograd of F.conv2d on bf16-representable operands, and against the first-generation
-    kernel; ragged pixel slabs, stride 2, Cout not a multiple of 128."""
+    kernel; ragged pixel slabs, stride 2, Cout not a multiple of 128.  Each pass asserts by dispatch counter which kernel ran
+    (tests/test_gpu_wgrad_exact.py pins every route exactly; the tolerances here are for random data)."""
     from monoflex_amd import autograd as AG, lib as L
+    # the kernel of the (1, 2, 0) passes.  Rows that cannot reach the route their pass names run the first-generation kernel there and are
+    # then compared with themselves (M = 3 * Ho * Wo pixels, K = 9 * cin):
+    #   128 -> 128 s2 @ 64x80   M = 3840 < 4096 and stride 2: neither the patch form (s1 only) nor the transposed-read form (M >= 4096)
+    #   512 -> 512 @ 12x40      M = 1440: below the patch form's 2048 and the transposed-read form's 4096
+    #   cout = 27 (padded 32), cin = 16 / 32 rows: the patch form runs, the transposed-read form does not (Cout % 64 != 0, K % 192 != 0)
+    route = {(128, 128, 2): ("mfma", "mfma", "mfma"), (512, 512, 1): ("mfma", "mfma", "mfma")}.get(
+        (cin, cout, stride), ("patch", "tr" if cin % 64 == 0 and cout % 64 == 0 else "mfma", "mfma"))
+    names = ("wgrad_patch", "wgrad_tr", "wgrad_mfma", "wgrad_valu")
     g = torch.Generator().manual_seed(31)
     B = 3
     x = torch.randn(B, cin, H, W, generator=g).to(DT[half]).float()
@@ -1307,13 +1316,16 @@ def test_conv_wgrad_transposed_read_kernel_vs_torch(cin, cout, k, stride, H, W, 
     lib_ = L.load()
     got = {}
     try:
-        for tr in (1, 2, 0):                                     # 1: LDS-patch form where it applies, 2: plain transposed-read form, 0: first generation
-            L.check(lib_.mfx_set_option(b"wgrad_tr", 1 if tr else 0), "opt")
+        for tr, want in zip((1, 2, 0), route):                   # 1: LDS-patch form where it applies, 2: plain transposed-read form, 0: first generation
+            L.check(lib_.mfx_set_option(b"wgrad_tr", tr), "opt")  # (2: the transposed-read kernel also where Cout % 128 != 0 -- the 64 -> 64 and 64 -> 192 rows)
             L.check(lib_.mfx_set_option(b"wgrad_patch", 1 if tr == 1 else 0), "opt")
             xd = _nhwc(x).to(DEV).to(DT[half])
             wd = w.to(DEV).requires_grad_()
             yd = AG.conv2d(xd, wd, None, stride, k // 2)
+            before = {n: lib_.mfx_get_counter(n.encode()) for n in names}
             (yd.float() * _nhwc(r).to(DEV)).sum().backward()
+            moved = {n: lib_.mfx_get_counter(n.encode()) - before[n] for n in names}
+            assert moved == {n: int(n == "wgrad_" + want) for n in names}, (tr, want, moved)
             got[tr] = wd.grad.detach().cpu()
     finally:
         L.check(lib_.mfx_set_option(b"wgrad_tr", 1), "opt")
