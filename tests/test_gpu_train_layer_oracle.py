@@ -34,7 +34,8 @@ the biased variance, (d) AdamW with L2 instead of decoupled weight decay.
 
 Not restated here, only counted (calls and dispatch families): the heads' fused nodes (FanOutConvFn, HeadConvGatherFn, EdgeScatterAddFn,
 GramRegHeadsHipFn) and the fused focal / object losses; so neither is the gradient they hand the backbone's output, nor p.grad of the parameters they
-consume.  Their references are the next step of this walk."""
+consume.  GramRegHeadsHipFn has its own float64 reference at small shapes: tests/test_gpu_gram_heads_oracle.py (tests/gram_heads_ref.py); the other fused
+head nodes stay counted only -- they are made of kernels that are pinned exactly."""
 import json
 import os
 import time

@@ -75,12 +75,10 @@ def test_autocorrelation_gradient_is_the_symmetrised_5x5_kernel():
     assert torch.allclose(dx, x.grad, atol=1e-10)
 
 
-def test_gram_reg_heads_node_end_to_end_on_cpu(monkeypatch):
-    """The WHOLE GramRegHeadsFn (forward table, extra activation rows, running statistics, every gradient) on the CPU against the dense layers in
-    fp64 torch, with the node's three library launches swapped for torch equivalents (the 5x5 autocorrelation, the column sums, the 5x5
-    gradient conv): the node's algebra and index plumbing are checked by the CPU suite, the launches themselves by the -m gpu tests."""
+def patch_library_launches(monkeypatch):
+    """Swap GramRegHeadsFn's three library launches (the 5x5 autocorrelation, the column sums, the 5x5 gradient conv) for torch equivalents, so
+    that the node runs on the CPU (shared with test_gram_heads_ref_cpu)."""
     from types import SimpleNamespace
-    from monoflex_amd.model.head.detector_predictor import InPlaceABN
     monkeypatch.setattr(GH, "_autocorr5", lambda x: _autocorr5(x.double()).float())
     monkeypatch.setattr(GH.AG, "_colsum", lambda t: t.reshape(-1, t.shape[-1]).double().sum(0).float())
     monkeypatch.setattr(GH.AG, "_c", lambda t: t.contiguous())
@@ -90,6 +88,14 @@ def test_gram_reg_heads_node_end_to_end_on_cpu(monkeypatch):
         y = F.conv2d(x.permute(0, 3, 1, 2).double(), p.w.double(), None, 1, p.pad) * p.scale.double().view(1, -1, 1, 1) + p.shift.double().view(1, -1, 1, 1)
         return y.permute(0, 2, 3, 1).float().contiguous()
     monkeypatch.setattr(GH.ops, "conv2d", conv2d)
+
+
+def test_gram_reg_heads_node_end_to_end_on_cpu(monkeypatch):
+    """The WHOLE GramRegHeadsFn (forward table, extra activation rows, running statistics, every gradient) on the CPU against the dense layers in
+    fp64 torch, with the node's three library launches swapped for torch equivalents (the 5x5 autocorrelation, the column sums, the 5x5
+    gradient conv): the node's algebra and index plumbing are checked by the CPU suite, the launches themselves by the -m gpu tests."""
+    from monoflex_amd.model.head.detector_predictor import InPlaceABN
+    patch_library_launches(monkeypatch)
 
     g = torch.Generator().manual_seed(31)
     B, H, W, Cin, C, N, R2 = 2, 7, 9, 8, 16, 10, 23
