@@ -82,7 +82,7 @@ int mfx_commit_options(void);
  *   that took the two-launch form), "conv_bn_stats" (convs whose epilogue accumulated the following BN's statistics);
  *   DCN backward: "dcn_bt_tile" (dcn_bwd_tile_kernel), "dcn_bt_sample" (dcn_bwd_sample_kernel), "dcn_bt_far" (far-corner kernels, both forms);
  *   "gram" (mfx_gram_heads phase calls), "adamw_multi" (one-launch AdamW), "optim_multi" (mfx_optim_multi: the one-launch update with a rule
- *   and / or a gradient coefficient), "grad_norm_multi" (mfx_grad_norm_multi: the gradient norm of the clipped update).
+ *   and / or a gradient coefficient), "optim_multi_sched" (mfx_optim_multi_sched: that update with beta1 read from the device), "grad_norm_multi" (mfx_grad_norm_multi: the gradient norm of the clipped update).
  * Post-processing: "box_nms" (launches of mfx_box_nms: one per call that had rows, whatever B), "decode_multi" (launches of
  *   mfx_decode_boxes_multi: one per call with B > 0; the default inference path never takes it).
  * Unknown names return MFX_ERR_ARG (negative). */
@@ -519,6 +519,21 @@ int mfx_adamw_multi(const mfx_adamw_desc* descs_dev, const long long* prefix_dev
 #define MFX_OPTIM_ADAM_L2 1
 int mfx_optim_multi(const mfx_adamw_desc* descs_dev, const long long* prefix_dev, int n, long long total_chunks,
                     const mfx_adamw_group* groups_dev, int rule, const float* grad_coef, const float* found_inf, void* stream);
+/* The same launch with beta1 read from the device, as lr is (SOLVER.OPTIMIZER 'adam_onecycle': the reference's fastai OptimWrapper over optim.Adam,
+ * solver/fastai_optim.py, whose OneCycle schedule moves Adam's beta1 together with the learning rate every iteration; a host float would be baked
+ * into a captured launch).  `beta1_dev`: device table of one `const float*` per group; the group record's `beta1` is not read: 1 - beta1 and
+ * beta1^t are taken from (double)*beta1_dev[group].
+ *   rule       the two above, or MFX_OPTIM_ADAM_TRUE_WD (2), the wrapper's "true weight decay": p *= (float)(1 - weight_decay * lr) (taken in
+ *              double and rounded once: the product of `p.data.mul_(1 - wd * lr)`), then Adam's moments on the UNMODIFIED gradient and the same
+ *              bias-corrected step.  A set `found_inf` skips the shrink with everything else.
+ *   rows       a descriptor with group < 0 is NORM-ONLY: mfx_grad_norm_multi counts its gradient, the update leaves it alone (p, m, v, step may be
+ *              NULL) -- the reference clips over model.parameters(), which holds parameters its wrapper's groups do not.  Under rule 2 a descriptor
+ *              with g == NULL is DECAY-ONLY: its parameter is shrunk and nothing else happens (m, v, step may be NULL; its norm share is 0).
+ * Own counter: "optim_multi_sched". */
+#define MFX_OPTIM_ADAM_TRUE_WD 2
+int mfx_optim_multi_sched(const mfx_adamw_desc* descs_dev, const long long* prefix_dev, int n, long long total_chunks,
+                          const mfx_adamw_group* groups_dev, const float* const* beta1_dev, int rule, const float* grad_coef, const float* found_inf,
+                          void* stream);
 /* Gradient-norm clipping of that update (reference engine/trainer.py:119 torch.nn.utils.clip_grad_norm_, norm type 2) over the same tables:
  * one workgroup per chunk sums the squares of its gradient elements in fp32 (16 per thread in series, then a fixed tree) and stores one partial
  * in `workspace` (mfx_grad_norm_workspace_bytes(total_chunks) bytes); one workgroup then adds the partials in a fixed order in double and writes

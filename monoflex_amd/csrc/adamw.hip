@@ -19,6 +19,17 @@
 //             lane) and grad_norm_finish_kernel (one workgroup: partials added in a fixed order in double).  No atomics anywhere, so the norm
 //             is the same bits in every run, eager or replayed, and on every rank holding the same (all-reduced) gradients.
 // Both are template parameters: <MFX_OPTIM_ADAMW, false> compiles to the expressions that were here before them (mfx_adamw_multi: same launches, same bits).
+//
+// One-cycle recipe (mfx_optim_multi_sched: SOLVER.OPTIMIZER 'adam_onecycle', the reference's fastai OptimWrapper over optim.Adam, solver/fastai_optim.py):
+//   RULE      MFX_OPTIM_ADAM_TRUE_WD: p *= shrink with shrink = (float)(1 - wd lr) taken in double -- the rounding of the wrapper's `p.data.mul_(1 - wd * lr)`,
+//             a product, not p - decay p -- then Adam's moments on the unmodified gradient and the bias-corrected step.
+//   DEVB1     beta1 is read from the device like lr (a table of one pointer per group): the one-cycle schedule moves it every iteration, and a host
+//             float would be baked into a captured launch.  1 - b1 and b1^t come from (double)*beta1.  A template parameter as COEF is: the
+//             instantiations without it read the group record's host float as before.
+//   rows      group < 0 marks a NORM-ONLY row (a gradient the clip's norm covers although the optimizer does not hold its parameter: the update
+//             returns for its chunks, p / m / v / step may be null).  g == null marks a DECAY-ONLY row of the true-weight-decay rule (a held parameter
+//             without a gradient: the wrapper shrinks it all the same and Adam skips it; m / v / step may be null, the norm counts it as zero).
+//             The drivers of the two older rules mark no row.
 #include "../../include/monoflex_hip.h"
 #include "err.h"
 #include "common.h"
@@ -29,7 +40,8 @@ constexpr int AW_CHUNK = 4096;
 
 __global__ __launch_bounds__(256) void adamw_bump_steps_kernel(const mfx_adamw_desc* __restrict__ descs, int n, const float* __restrict__ found_inf) {
     if (found_inf && *found_inf != 0.f) return;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) *descs[i].step += 1.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x)
+        if (descs[i].step) *descs[i].step += 1.f;                              // (norm-only and decay-only rows have no counter)
 }
 
 // the tensor that owns chunk `chunk`: the last i with prefix[i] <= chunk (one ballot per 256 table entries; all 256 threads call this)
@@ -44,28 +56,36 @@ __device__ __forceinline__ int chunk_owner(const long long* __restrict__ prefix,
     return below[0] + below[1] + below[2] + below[3] - 1;
 }
 
-template <int RULE, bool COEF>
+template <int RULE, bool COEF, bool DEVB1>
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const mfx_adamw_desc* __restrict__ descs, const long long* __restrict__ prefix, int n,
                                                          const mfx_adamw_group* __restrict__ groups, const float* __restrict__ found_inf,
-                                                         const float* __restrict__ grad_coef) {
+                                                         const float* __restrict__ grad_coef, const float* const* __restrict__ beta1_tab) {
     if (found_inf && *found_inf != 0.f) return;
     __shared__ int below[4];
     const long chunk = blockIdx.x;
     const int ti = chunk_owner(prefix, n, chunk, below);
     const mfx_adamw_desc d = descs[ti];
+    if (d.group < 0) return;                                                  // a norm-only row (uniform per workgroup)
     const mfx_adamw_group gr = groups[d.group];
     const long j0 = (chunk - (long)prefix[ti]) * AW_CHUNK;
     const long j1 = j0 + AW_CHUNK < d.numel ? j0 + AW_CHUNK : d.numel;
+    float* p = reinterpret_cast<float*>(d.p);
+    const float* g = reinterpret_cast<const float*>(d.g);
     // scalars of the step (uniform per tensor)
-    const double lr = (double)*gr.lr, b1 = (double)gr.beta1, b2 = (double)gr.beta2;
+    const float fb1 = DEVB1 ? *beta1_tab[d.group] : gr.beta1;
+    const double lr = (double)*gr.lr, b1 = (double)fb1, b2 = (double)gr.beta2;
+    const float shrink = (float)(1.0 - (double)gr.weight_decay * lr);         // (MFX_OPTIM_ADAM_TRUE_WD only)
+    if (RULE == MFX_OPTIM_ADAM_TRUE_WD && g == nullptr) {                     // a decay-only row: the same elements in the same order, one product each
+        for (long j = j0 + (long)threadIdx.x * 4; j < j1; j += 1024)
+            for (long e = j; e < j + 4 && e < j1; ++e) p[e] *= shrink;
+        return;
+    }
     const double t = (double)*d.step;                                         // already advanced (adamw_bump_steps_kernel)
     const float decay = (float)(lr * (double)gr.weight_decay);
     const float step_size = (float)(lr / (1.0 - pow(b1, t)));
     const float bc2_sqrt = (float)sqrt(1.0 - pow(b2, t));
-    const float w1 = (float)(1.0 - b1), fb1 = gr.beta1, fb2 = gr.beta2, w2 = (float)(1.0 - b2), eps = gr.eps;
+    const float w1 = (float)(1.0 - b1), fb2 = gr.beta2, w2 = (float)(1.0 - b2), eps = gr.eps;
     const float wd = gr.weight_decay, coef = COEF ? *grad_coef : 1.f;
-    float* p = reinterpret_cast<float*>(d.p);
-    const float* g = reinterpret_cast<const float*>(d.g);
     float* m = reinterpret_cast<float*>(d.m);
     float* v = reinterpret_cast<float*>(d.v);
     auto upd = [&](float& pp, float gg, float& mm, float& vv) {
@@ -74,7 +94,10 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const mfx_adamw_desc* 
             asm volatile("" : "+v"(gg));              // the scaled gradient is a finished fp32 value, as if read back from memory: what follows is the
         }                                             // expression the unscaled kernel evaluates (coef == 1 gives the unclipped step's bits)
         if (RULE == MFX_OPTIM_ADAM_L2) gg += wd * pp;
-        else pp -= decay * pp;
+        else if (RULE == MFX_OPTIM_ADAM_TRUE_WD) {
+            pp *= shrink;
+            asm volatile("" : "+v"(pp));              // a finished fp32 product (`mul_`), not to be contracted into the step's subtraction
+        } else pp -= decay * pp;
         mm = fb1 * mm + w1 * gg;
         vv = fb2 * vv + w2 * gg * gg;
         pp -= step_size * mm / (sqrtf(vv) / bc2_sqrt + eps);
@@ -114,7 +137,7 @@ __global__ __launch_bounds__(256) void grad_sq_partials_kernel(const mfx_adamw_d
     const float* g = reinterpret_cast<const float*>(d.g);
     const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
     float s = 0.f;
-    long j = j0 + (long)threadIdx.x * 4;
+    long j = g ? j0 + (long)threadIdx.x * 4 : j1;                              // (a decay-only row has no gradient: its partial is 0)
     if (vec) {
         for (; j + 4 <= j1; j += 1024) {
             const f32x4 gv = *reinterpret_cast<const f32x4*>(g + j);
@@ -166,8 +189,8 @@ extern "C" int mfx_adamw_multi(const mfx_adamw_desc* descs_dev, const long long*
     if (total_chunks >= (1LL << 31)) return mfx_fail(MFX_ERR_ARG, "adamw_multi: too many chunks");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(adamw_bump_steps_kernel, dim3(1), dim3(256), 0, st, descs_dev, n, found_inf);
-    hipLaunchKernelGGL((adamw_multi_kernel<MFX_OPTIM_ADAMW, false>), dim3((unsigned)total_chunks), dim3(256), 0, st, descs_dev, prefix_dev, n, groups_dev, found_inf,
-                       (const float*)nullptr);
+    hipLaunchKernelGGL((adamw_multi_kernel<MFX_OPTIM_ADAMW, false, false>), dim3((unsigned)total_chunks), dim3(256), 0, st, descs_dev, prefix_dev, n, groups_dev,
+                       found_inf, (const float*)nullptr, (const float* const*)nullptr);
     ++g_cnt_adamw_multi;
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
@@ -182,11 +205,34 @@ extern "C" int mfx_optim_multi(const mfx_adamw_desc* descs_dev, const long long*
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(adamw_bump_steps_kernel, dim3(1), dim3(256), 0, st, descs_dev, n, found_inf);
 #define MFX_OPTIM_LAUNCH(R_, C_) \
-    hipLaunchKernelGGL((adamw_multi_kernel<R_, C_>), dim3((unsigned)total_chunks), dim3(256), 0, st, descs_dev, prefix_dev, n, groups_dev, found_inf, grad_coef)
+    hipLaunchKernelGGL((adamw_multi_kernel<R_, C_, false>), dim3((unsigned)total_chunks), dim3(256), 0, st, descs_dev, prefix_dev, n, groups_dev, found_inf, grad_coef, \
+                       (const float* const*)nullptr)
     if (rule == MFX_OPTIM_ADAMW) { if (grad_coef) MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAMW, true); else MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAMW, false); }
     else { if (grad_coef) MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAM_L2, true); else MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAM_L2, false); }
 #undef MFX_OPTIM_LAUNCH
     ++g_cnt_optim_multi;
+    MFX_HIP_CHECK(hipGetLastError());
+    return MFX_OK;
+}
+
+extern "C" int mfx_optim_multi_sched(const mfx_adamw_desc* descs_dev, const long long* prefix_dev, int n, long long total_chunks,
+                                     const mfx_adamw_group* groups_dev, const float* const* beta1_dev, int rule, const float* grad_coef, const float* found_inf,
+                                     void* stream) {
+    if (rule != MFX_OPTIM_ADAMW && rule != MFX_OPTIM_ADAM_L2 && rule != MFX_OPTIM_ADAM_TRUE_WD)
+        return mfx_fail(MFX_ERR_ARG, "optim_multi_sched: rule must be 0 (AdamW), 1 (Adam with L2 decay) or 2 (Adam with true weight decay)");
+    if (n <= 0 || total_chunks <= 0) return MFX_OK;
+    if (!descs_dev || !prefix_dev || !groups_dev || !beta1_dev) return mfx_fail(MFX_ERR_ARG, "optim_multi_sched: null pointer");
+    if (total_chunks >= (1LL << 31)) return mfx_fail(MFX_ERR_ARG, "optim_multi_sched: too many chunks");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(adamw_bump_steps_kernel, dim3(1), dim3(256), 0, st, descs_dev, n, found_inf);
+#define MFX_OPTIM_LAUNCH(R_, C_) \
+    hipLaunchKernelGGL((adamw_multi_kernel<R_, C_, true>), dim3((unsigned)total_chunks), dim3(256), 0, st, descs_dev, prefix_dev, n, groups_dev, found_inf, grad_coef, \
+                       beta1_dev)
+    if (rule == MFX_OPTIM_ADAMW) { if (grad_coef) MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAMW, true); else MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAMW, false); }
+    else if (rule == MFX_OPTIM_ADAM_L2) { if (grad_coef) MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAM_L2, true); else MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAM_L2, false); }
+    else { if (grad_coef) MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAM_TRUE_WD, true); else MFX_OPTIM_LAUNCH(MFX_OPTIM_ADAM_TRUE_WD, false); }
+#undef MFX_OPTIM_LAUNCH
+    ++g_cnt_optim_multi_sched;
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }

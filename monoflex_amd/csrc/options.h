@@ -129,6 +129,7 @@
     X(gram, "phase calls of mfx_gram_heads on 16-bit maps") \
     X(adamw_multi, "calls of mfx_adamw_multi") \
     X(optim_multi, "calls of mfx_optim_multi (the one-launch update with a rule / a gradient coefficient)") \
+    X(optim_multi_sched, "calls of mfx_optim_multi_sched (the one-launch update reading beta1 from the device)") \
     X(grad_norm_multi, "calls of mfx_grad_norm_multi")
 
 #define MFX_DECLARE_OPTION(name, def, lo, hi, doc) extern int g_opt_##name;

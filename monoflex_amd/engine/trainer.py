@@ -257,6 +257,9 @@ class GraphedTrainStep:
             if not torch.is_tensor(g["lr"]):
                 raise ValueError("GraphedTrainStep: the learning rate must be a device scalar (solver.build_optimizer(capturable=True)); "
                                  "a Python float would be baked into the captured optimizer step")
+            if "mom" in g and not torch.is_tensor(g["mom"]):           # solver.OptimWrapper ('adam_onecycle'): the schedule moves Adam's beta1 too
+                raise ValueError("GraphedTrainStep: the wrapper's momentum must be a device scalar (solver.build_optimizer(capturable=True)); "
+                                 "a Python float would be baked into the captured optimizer step")
         # The capture needs warm-up runs (lazy allocations, the optimizer's state tensors, RCCL's first-call setup), and those are
         # real optimisation steps on batch 0.  They must not count: the state they touch (parameters, BN buffers incl. running
         # statistics and num_batches_tracked, AdamW moments and step counters, the loss scale) is snapshotted here and written back
@@ -287,6 +290,8 @@ class GraphedTrainStep:
             torch.cuda.synchronize()
 
     def _snapshot_state(self):
+        # (the device-scalar learning rates -- and the one-cycle wrapper's `mom` -- are not part of it: nothing inside `_eager` writes them, the
+        # schedulers are stepped by the caller between steps)
         with torch.no_grad():
             return {"params": [p.detach().clone() for p in self.net.parameters()],
                     "buffers": [b.detach().clone() for b in self.net.buffers()],

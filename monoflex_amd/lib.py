@@ -187,6 +187,7 @@ SYMBOLS = {
     "mfx_adamw_chunk_elems": (_I, []),
     "mfx_adamw_multi": (_I, [_P, _P, _I, ctypes.c_longlong, _P, _P, _P]),
     "mfx_optim_multi": (_I, [_P, _P, _I, ctypes.c_longlong, _P, _I, _P, _P, _P]),
+    "mfx_optim_multi_sched": (_I, [_P, _P, _I, ctypes.c_longlong, _P, _P, _I, _P, _P, _P]),
     "mfx_grad_norm_workspace_bytes": (_S, [ctypes.c_longlong]),
     "mfx_grad_norm_multi": (_I, [_P, _P, _I, ctypes.c_longlong, _F, _P, _S, _P, _P, _P]),
     "mfx_colsum": (_I, [_P, _P, ctypes.c_long, _I, _I, _I, _P]),
@@ -281,6 +282,7 @@ HEAD_OPTIONAL = ('depth_uncertainty', 'corner_offset', 'corner_uncertainty')
 REG_LOSSES = ('L1', 'smooth_l1')
 DEPTH_LOSSES = ('L1', 'log', 'inv_sig')
 OPTIM_ADAMW, OPTIM_ADAM_L2 = 0, 1                                # mfx_optim_multi `rule`
+OPTIM_ADAM_TRUE_WD = 2                                           # ... and mfx_optim_multi_sched's third
 CORNER_DEPTHS = ('direct', 'keypoint_mean', 'soft_combine', 'hard_combine')        # mfx_object_loss_cfg.corner_depth_mode
 LOSS_REQUIRED = ('hm_loss', 'bbox_loss', 'depth_loss', 'offset_loss', 'orien_loss', 'dims_loss')
 LOSS_OPTIONAL = ('corner_loss', 'trunc_offset_loss', 'keypoint_loss', 'keypoint_depth_loss', 'weighted_avg_depth_loss')

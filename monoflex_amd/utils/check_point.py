@@ -53,6 +53,10 @@ def optimizer_state_to_reference(model, optimizer):
     """optimizer.state_dict() re-expressed with one param group per parameter in named_parameters() order."""
     sd = optimizer.state_dict()
     names = _trainable_names(model)
+    if _is_onecycle_wrapper(optimizer):
+        # SOLVER.OPTIMIZER 'adam_onecycle': this build's groups ARE the reference's (non-BN leaves / BN leaves, solver.onecycle_param_groups); only the
+        # device scalars (lr, mom) become plain numbers
+        return {"state": sd["state"], "param_groups": [{k: (v if k == "params" else _scalar(v)) for k, v in g.items()} for g in sd["param_groups"]]}
     if len(sd["param_groups"]) == len(names):
         return sd
     loc = _local_index(model, optimizer)
@@ -67,7 +71,12 @@ def optimizer_state_to_reference(model, optimizer):
     return {"state": state, "param_groups": groups}
 
 
-NUMERIC_HYPER = ("lr", "betas", "eps", "weight_decay", "amsgrad", "initial_lr", "momentum", "dampening", "nesterov", "maximize")
+NUMERIC_HYPER = ("lr", "betas", "eps", "weight_decay", "amsgrad", "initial_lr", "momentum", "dampening", "nesterov", "maximize", "mom")
+
+
+def _is_onecycle_wrapper(optimizer):
+    from ..solver import OptimWrapper
+    return isinstance(optimizer, OptimWrapper)
 
 
 def _scalar(v):
@@ -82,14 +91,21 @@ def _keep_build_flags(mine_group, saved_group):
     for k in NUMERIC_HYPER:
         if k in saved_group:
             g[k] = _scalar(saved_group[k])
+    if "mom" in g and "mom" not in saved_group and "betas" in saved_group:      # a file written by the reference's wrapper: its momentum is betas[0]
+        g["mom"] = float(saved_group["betas"][0])
     return g
 
 
 def load_optimizer_state(optimizer, sd):
-    """optimizer.load_state_dict(sd) that keeps device-scalar learning rates (solver.build_optimizer(capturable=True)) as the same
-    tensor objects a captured graph reads, filled with the loaded values."""
+    """optimizer.load_state_dict(sd) that keeps device-scalar learning rates (solver.build_optimizer(capturable=True)) -- and the one-cycle wrapper's
+    device-scalar `mom` -- as the same tensor objects a captured graph reads, filled with the loaded values."""
     lr_tensors = [(g["lr"], g.get("initial_lr")) for g in optimizer.param_groups]
+    mom_tensors = [g.get("mom") for g in optimizer.param_groups]
     optimizer.load_state_dict(sd)
+    for g, mom in zip(optimizer.param_groups, mom_tensors):
+        if torch.is_tensor(mom) and g.get("mom") is not mom:
+            mom.fill_(float(g.get("mom", g["betas"][0])))
+            g["mom"] = mom
     for g, (lr, init) in zip(optimizer.param_groups, lr_tensors):
         if torch.is_tensor(lr):
             lr.fill_(float(g["lr"]))
