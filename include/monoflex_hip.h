@@ -906,6 +906,22 @@ int mfx_kitti_preprocess_u8(const uint8_t* pixels, const int64_t* offsets, const
 int mfx_kitti_preprocess_u8_bgr(const uint8_t* pixels, const int64_t* offsets, const int32_t* img_wh, const int32_t* flip,
                                 float* out, int B, int in_w, int in_h, const float* mean3, const float* std3, void* stream);
 
+/* The two conversions from a resident store: the raw inputs of N samples stay on the device and a batch of B slots is assembled
+ * by index, slot b showing store row index[b] (DATALOADER.RESIDENT, monoflex_amd/data/resident.py).
+ *   index, flip: (B) int32 on the device.  Everything the entries above read per sample other than `flip` is store-sized:
+ *   pixels / offsets (N) / img_wh (N,2) here, and for the targets the descriptor's records (N,max_objs,14), n_obj (N), P (N,3,4),
+ *   img_wh (N,2) and `right` (N).  d->flip, d->B and every output of the descriptor are batch-sized, as before.
+ * Slot b is computed exactly as the entries above compute sample b of a batch holding row index[b] with flip[b] (the same
+ * arithmetic, the same three launches); a row may appear in several slots, with different flips.  An index[b] outside [0, N) is
+ * not dereferenced: status[b] = 16 (bit 4) and every other output of the slot, the frame included, is zero.
+ * cfg == NULL and right == NULL mean what they mean at mfx_kitti_encode_targets_cfg; to_bgr != 0 is mfx_kitti_preprocess_u8_bgr.
+ * The index travels beside the descriptor, as `right` and `cfg` do: mfx_kitti_desc and MFX_ABI_VERSION are unchanged. */
+int mfx_kitti_preprocess_u8_indexed(const uint8_t* pixels, const int64_t* offsets, const int32_t* img_wh, const int32_t* index,
+                                    const int32_t* flip, float* out, int B, int N, int in_w, int in_h, const float* mean3,
+                                    const float* std3, int to_bgr, void* stream);
+int mfx_kitti_encode_targets_indexed(const mfx_kitti_desc* d, const int32_t* index, int32_t N, const int32_t* right,
+                                     const mfx_kitti_encode_cfg* cfg, void* stream);
+
 /* ---- (5) KITTI AP evaluation on the device -----------------------------------------------------------------------------
  * Replaces the numba CPU loops and the numba.cuda rotated-IoU kernel of the reference's evaluator
  * (data/datasets/evaluation/kitti_object_eval_python/eval.py:27-286,448-570, rotate_iou.py:17-333). The host parses the

@@ -142,7 +142,12 @@ def _defaults():
         MOMS=[0.95, 0.85], PCT_START=0.4, DIV_FACTOR=10, STEPS=(20000, 25000), LR_CLIP=0.0000001, WARMUP_EPOCH=1,
         GRAD_CLIP_FACTOR=99, GRAD_ALPHA=0.9, MASTER_BATCH=-1, MOMENTUM=0.9,
     ))
-    C.DATALOADER = CfgNode(dict(NUM_WORKERS=8, SIZE_DIVISIBILITY=0, ASPECT_RATIO_GROUPING=False))
+    C.DATALOADER = CfgNode(dict(
+        NUM_WORKERS=8, SIZE_DIVISIBILITY=0, ASPECT_RATIO_GROUPING=False,
+        # build-specific: decode the split once, keep it on the device and assemble batches from it by index (data/resident.py);
+        # RESIDENT_MAX_GB bounds the pixel arena of one store
+        RESIDENT=False, RESIDENT_MAX_GB=64,
+    ))
     C.TEST = CfgNode(dict(
         SINGLE_GPU_TEST=True, IMS_PER_BATCH=1, PRED_2D=True, UNCERTAINTY_AS_CONFIDENCE=False,
         METRIC=['R40'], EVAL_DIS_IOUS=False, EVAL_DEPTH=False, DETECTIONS_PER_IMG=50,

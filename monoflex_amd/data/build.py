@@ -1,12 +1,14 @@
 """Loader construction with the reference's names (data/build.py:17-180): `make_data_loader(cfg, is_train)` and
 `build_test_loader(cfg)`.  Dataset roots come from `DatasetCatalog` (config/paths_catalog.py:3-27): DATA_DIR is
 $MONOFLEX_DATA_DIR (default ./datasets) + `kitti/object/{training,testing}/`.  Workers only read files; the batch is encoded
-on the device by DeviceLoader (collate_batch.py)."""
+on the device by DeviceLoader (collate_batch.py).  With DATALOADER.RESIDENT the loaders are ResidentLoaders (resident.py): the
+split is decoded once into a device store that lives with the loader, and batches are assembled from it by index."""
 import os
 
 from ..utils.comm import get_world_size
 from .collate_batch import DeviceLoader
 from .datasets.kitti import KITTIDataset
+from .resident import ResidentLoader
 from .samplers import InferenceSampler, IterationBatchSampler, TrainingSampler
 
 
@@ -29,6 +31,18 @@ def build_dataset(cfg, is_train=True, device=None):
             for n in names]
 
 
+def _workers(cfg):
+    return int(cfg.get("DATALOADER", {}).get("NUM_WORKERS", 4))
+
+
+def _resident(cfg):
+    """None, or the keywords of a ResidentLoader's store build when DATALOADER.RESIDENT is set."""
+    dl = cfg.get("DATALOADER", {})
+    if not dl.get("RESIDENT", False):
+        return None
+    return dict(num_workers=_workers(cfg), max_bytes=int(float(dl.get("RESIDENT_MAX_GB", 64)) * (1 << 30)))
+
+
 def make_data_loader(cfg, is_train=True):
     world = get_world_size()
     per_batch = cfg.SOLVER.IMS_PER_BATCH if is_train else cfg.TEST.IMS_PER_BATCH
@@ -37,7 +51,11 @@ def make_data_loader(cfg, is_train=True):
     for ds in build_dataset(cfg, is_train):
         sampler = TrainingSampler(len(ds))                       # one shared endless permutation stream, rank r takes r::world
         bs = IterationBatchSampler(sampler, per_batch // world, num_iterations=int(cfg.SOLVER.MAX_ITERATION))
-        loaders.append(DeviceLoader(ds, batch_sampler=bs, num_workers=int(cfg.get("DATALOADER", {}).get("NUM_WORKERS", 4))))
+        resident = _resident(cfg)
+        if resident is not None:                                # the shared permutation can hand any rank any sample: the whole split
+            loaders.append(ResidentLoader(ds, batch_sampler=bs, **resident))
+        else:
+            loaders.append(DeviceLoader(ds, batch_sampler=bs, num_workers=_workers(cfg)))
     if is_train:
         assert len(loaders) == 1
         return loaders[0]
@@ -45,6 +63,9 @@ def make_data_loader(cfg, is_train=True):
 
 
 def build_test_loader(cfg, is_train=False):
-    return [DeviceLoader(ds, batch_size=cfg.TEST.IMS_PER_BATCH, sampler=InferenceSampler(len(ds)),
-                         num_workers=int(cfg.get("DATALOADER", {}).get("NUM_WORKERS", 4)))
+    resident = _resident(cfg)
+    if resident is not None:                                    # the store covers this rank's shard of the split
+        return [ResidentLoader(ds, batch_size=cfg.TEST.IMS_PER_BATCH, sampler=InferenceSampler(len(ds)), **resident)
+                for ds in build_dataset(cfg, is_train)]
+    return [DeviceLoader(ds, batch_size=cfg.TEST.IMS_PER_BATCH, sampler=InferenceSampler(len(ds)), num_workers=_workers(cfg))
             for ds in build_dataset(cfg, is_train)]

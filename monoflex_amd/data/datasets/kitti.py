@@ -119,11 +119,16 @@ class KITTIDataset(torch.utils.data.Dataset):
         views = dict(rights=[s.right for s in samples]) if self.use_right_img else {}
         fields = encode_targets([s.records for s in samples], [s.calib.P for s in samples], sizes, flips, self.params,
                                 self.device, check=check, **views)
+        targets = self.make_targets(fields, [s.calib for s in samples], sizes, flips)
+        return images, targets, [s.original_idx for s in samples], fields
+
+    def make_targets(self, fields, calibs, sizes, flips):
+        """Stacked device fields + per-sample calibration, (w, h) and flip -> [ParamsList], one per sample of the batch."""
         test_split = self.split == "test"
         targets = []
-        for b, s in enumerate(samples):
+        for b, (c, flip) in enumerate(zip(calibs, flips)):
             t = ParamsList(image_size=(self.input_width, self.input_height), is_train=self.is_train)
-            calib = s.calib.flipped(sizes[b][0]) if s.flip else s.calib
+            calib = c.flipped(sizes[b][0]) if flip else c
             if test_split:                                                   # kitti.py:287-299
                 t.add_field("pad_size", fields["pad_size"][b])
                 t.add_field("calib", calib)
@@ -138,7 +143,7 @@ class KITTIDataset(torch.utils.data.Dataset):
                     if k == "locations":
                         t.add_field("calib", calib)                          # same position as in the reference's field list
             targets.append(t)
-        return images, targets, [s.original_idx for s in samples], fields
+        return targets
 
     def __getitem__(self, idx):
         images, targets, ids, _ = self.encode_batch([self.load_raw(idx)])

@@ -42,7 +42,8 @@ TARGET_FIELDS = {
 STATUS_MESSAGES = {1: "more objects of the detect classes than DATASETS.MAX_OBJECTS",
                    2: "truncated object whose 2D box centre lies outside the image (the reference fails on it)",
                    4: "truncated object: the centre line meets no image border",
-                   8: "boundary heat map with both radii > 0"}
+                   8: "boundary heat map with both radii > 0",
+                   16: "store row outside the resident store (mfx_kitti_encode_targets_indexed)"}
 
 
 class EncodeParams:
@@ -204,12 +205,14 @@ def encode_targets(records, Ps, sizes, flips, params, device, check=True, rights
     return prepared.out
 
 
-def check_status(status):
+def check_status(status, ids=None):
+    """ids: the sample ids of the batch, named in the message when given."""
     bad = torch.nonzero(status).flatten().tolist()
     if bad:
         code = int(status[bad[0]])
         msgs = [m for bit, m in STATUS_MESSAGES.items() if code & bit]
-        raise ValueError("target encoding failed for sample %d of the batch: %s" % (bad[0], "; ".join(msgs)))
+        who = "" if ids is None else " (id %s)" % (ids[bad[0]],)
+        raise ValueError("target encoding failed for sample %d of the batch%s: %s" % (bad[0], who, "; ".join(msgs)))
 
 
 def preprocess_images(frames, flips, params, device, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):

@@ -238,6 +238,8 @@ SYMBOLS = {
     "mfx_kitti_encode_targets_cfg": (_I, [ctypes.POINTER(KittiDesc), _P, ctypes.POINTER(KittiEncodeCfg), _P]),
     "mfx_kitti_preprocess_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.POINTER(c_float), ctypes.POINTER(c_float), _P]),
     "mfx_kitti_preprocess_u8_bgr": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.POINTER(c_float), ctypes.POINTER(c_float), _P]),
+    "mfx_kitti_preprocess_u8_indexed": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(c_float), ctypes.POINTER(c_float), _I, _P]),
+    "mfx_kitti_encode_targets_indexed": (_I, [ctypes.POINTER(KittiDesc), _P, ctypes.c_int32, _P, ctypes.POINTER(KittiEncodeCfg), _P]),
     "mfx_kitti_eval_overlaps": (_I, [ctypes.POINTER(KittiEvalDesc), _P]),
     "mfx_kitti_eval_match_pass1": (_I, [ctypes.POINTER(KittiEvalDesc), _P]),
     "mfx_kitti_eval_thresholds": (_I, [ctypes.POINTER(KittiEvalDesc), _P, _P]),
