@@ -243,6 +243,15 @@ typedef struct {
 int mfx_dcn_nhwc(const mfx_dcn_desc* d, void* stream);
 /* 1 when mfx_dcn_nhwc(d) will compute the offsets inside the kernel from off_w_frag_f16 / off_shift (d->offmask is not read), else 0 */
 int mfx_dcn_fuses_offset_conv(const mfx_dcn_desc* d);
+/* n <= 4 DCN modules of identical shape and dtype that read different maps (the proj modules of one IDAUp, dla_dcn.py:419-425), as two launches on
+ * `stream`: the n offset/mask convs off[0..n) in one grid, then the n gathers dcn[0..n) in one grid.  off[i] and dcn[i] are the descriptors the caller
+ * would give mfx_conv2d_nhwc and mfx_dcn_nhwc for module i (off[i].x == dcn[i].x, off[i].y == dcn[i].offmask, fp32 [M][32]); dcn[i].workspace is never written, it only tells whether mfx_dcn_nhwc would split K for the module.
+ * Every output element is computed by the instruction sequence of the one-module launches: results are bit-identical to them.
+ * Returns MFX_OK when the group ran; 1 = not applicable, NOTHING was launched and the caller runs the modules one by one (option "dcn_group" = 0,
+ * MFX_F32 / MFX_F16X2, nonsquare geometry, modules that differ in any size, a layer mfx_dcn_nhwc gives to the LDS / LDS-patch / wave kernels or runs split-K (small maps: another K order), an
+ * offset conv the compile-time-geometry 3x3 kernel has no grouped form for); < 0 = error.  The gather tile is chosen from the group's workgroup
+ * count (csrc/conv_kernels.hip: dispatch_dcn_group).  Counter "dcn_group" counts the groups that ran.  Descriptors and MFX_ABI_VERSION stay as they are. */
+int mfx_dcn_module_group(const mfx_conv_desc* off, const mfx_dcn_desc* dcn, int n, void* stream);
 
 /* DCNv2 as "project, then sample" (r06; 3x3 / stride 1 / pad 1 / dilation 1, 16-bit maps), the sampling half.  Bilinear interpolation commutes with the
  * contraction over input channels, so the module (dcn_v2_im2col_cuda.cu:125-195 + dcn_v2_cuda.cu:139-163) is

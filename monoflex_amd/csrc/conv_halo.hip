@@ -523,7 +523,8 @@ int try_conv_halo(const mfx_conv_desc* d, hipStream_t st, int* stats_ran) {
     return rc;
 }
 
-static int try_conv_halo_impl(const mfx_conv_desc* d, hipStream_t st) {
+// the variant this file picks for d, 0 where the halo kernels do not take it
+static int halo_pick_variant(const mfx_conv_desc* d) {
     if (g_opt_halo == 0) return 0;
     if (d->kh != 3 || d->kw != 3 || (d->stride != 1 && d->stride != 2) || d->pad_h != 1 || d->pad_w != 1 || d->dil_w != 1) return 0;
     if (d->stride == 2 && !g_opt_halo_s2) return 0;
@@ -560,6 +561,22 @@ static int try_conv_halo_impl(const mfx_conv_desc* d, hipStream_t st) {
         const int f = g_opt_halo - 1, bn = variant_bn(f);
         if (bn && N % bn == 0 && (bn >= 64) == (N >= 64)) v = f;
     }
+    return v;
+}
+
+// The offset/mask convs of a DCN module group in one launch: every conv must be one the compile-time-geometry kernel takes on its own, with one variant
+int try_conv_halo_group(const mfx_conv_desc* d, int n, hipStream_t st) {
+    if (n < 1 || n > kGroupMax || g_opt_halo_cg > 0) return 1;
+    const int v = halo_pick_variant(&d[0]);
+    if (v == 0) return 1;
+    for (int i = 1; i < n; ++i)
+        if (halo_pick_variant(&d[i]) != v) return 1;
+    return try_conv_cw_group(d, n, v, st);
+}
+
+static int try_conv_halo_impl(const mfx_conv_desc* d, hipStream_t st) {
+    const int v = halo_pick_variant(d);
+    if (v == 0) return 0;
     if ((d->dtype == MFX_BF16 || d->dtype == MFX_F16) && g_opt_halo_cg <= 0) {
         // compile-time-geometry form of the same decomposition (conv_cw.hip): bit-identical output
         const int r = try_conv_cw(d, v, st);

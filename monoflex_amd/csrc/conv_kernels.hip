@@ -283,6 +283,29 @@ __global__ __launch_bounds__(WM * WN * 64) void dcn_igemm_kernel(const T* x, con
                                          reinterpret_cast<T*>(ep.y), ep.ldy, m0, n0, g.M, ep.Cout, ep.act);
 }
 
+// Grouped form of dcn_igemm_kernel (mfx_dcn_module_group): n <= kGroupMax modules of one geometry and dtype that read different maps.  Workgroups
+// [i * tiles_per, (i + 1) * tiles_per) are module i's grid in the order its own launch gives them (xcd_remap inside the module).  The per-module pointers
+// come from the by-value table with a workgroup-uniform index (scalar loads from the kernel arguments); loaders, main loop and epilogue are the one-module
+// kernel's, so every output element sees the same operands in the same order.  No split-K: a group is launched to have enough workgroups without it.
+struct DcnGroupPtrs {
+    const void* x[kGroupMax]; const float* om[kGroupMax]; const void* w[kGroupMax]; const float* scale[kGroupMax]; const float* shift[kGroupMax]; void* y[kGroupMax];
+    int tiles_per;
+};
+template <typename T, int BM, int BN, int WM, int WN, int KC>
+__global__ __launch_bounds__(WM * WN * 64) void dcn_igemm_group_kernel(DcnGroupPtrs gp, DcnGeom g, EpiArgs ep) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int mod = blockIdx.x / gp.tiles_per, local = blockIdx.x - mod * gp.tiles_per;
+    const int tile = xcd_remap(local, gp.tiles_per);
+    const int tn = tile % ep.tiles_n, tm = tile / ep.tiles_n;
+    const int m0 = tm * BM, n0 = tn * BN;
+    DcnALoader<T, BM, WM * WN * 64, KC> al; al.init(reinterpret_cast<const T*>(gp.x[mod]), gp.om[mod], g, m0, threadIdx.x);
+    WeightLoader<T, BN, WM * WN * 64, KC> bl; bl.init(reinterpret_cast<const T*>(gp.w[mod]), n0, ep.K_pad, threadIdx.x);
+    f32x4 acc[BM / WM / 16][BN / WN / 16];
+    gemm_mainloop<T, BM, BN, WM, WN, KC>(al, bl, ep.nk, smem, acc);
+    epilogue_store<T, T, BM, BN, WM, WN>(acc, smem, gp.scale[mod], gp.shift[mod], nullptr, 0,
+                                         reinterpret_cast<T*>(gp.y[mod]), ep.ldy, m0, n0, g.M, ep.Cout, ep.act);
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch helpers + tile selection
 // ------------------------------------------------------------------------------------------------
@@ -508,6 +531,17 @@ extern "C" int mfx_cat_conv1x1_nhwc(const mfx_cat_desc* d, void* stream) {
 }
 
 namespace mfx {
+// split-K on small maps (12x40 .. 24x80: 60 .. 480 tiles with K = 2304 .. 4608): more workgroups, same gather work
+static int dcn_pick_ksplit(const mfx_dcn_desc* d, int M, int tiles, int nk) {
+    int ksplit = 1;
+    if (d->workspace && g_opt_dcn_ksplit != 1 && d->Cout == d->Cout_pad) {
+        ksplit = g_opt_dcn_ksplit > 1 ? g_opt_dcn_ksplit : (tiles <= 256 ? 3 : 1);   // layer_bench: 512->256@12x40 83 -> 58 us, 256->64@24x80 49 -> 39; 480-tile layers lose
+        ksplit = std::min(ksplit, std::min(9, nk / 4));
+        while (ksplit > 1 && ((nk + ksplit - 1) / ksplit) * (ksplit - 1) >= nk) --ksplit;
+        if ((size_t)ksplit * M * d->Cout_pad * sizeof(float) > (size_t)d->workspace_bytes) ksplit = 1;
+    }
+    return ksplit;
+}
 template <typename T, int BM, int BN, int WM, int WN, int KC>
 static int launch_dcn(const mfx_dcn_desc* d, const DcnGeom& g, EpiArgs ep, hipStream_t st) {
     ep.tiles_n = d->Cout_pad / BN;
@@ -517,14 +551,7 @@ static int launch_dcn(const mfx_dcn_desc* d, const DcnGeom& g, EpiArgs ep, hipSt
     constexpr int smem = TileSmem<BM, BN, KC>::bytes;
     static bool attr_set = false;
     if (!attr_set) { int rc = set_smem(k, smem); if (rc) return rc; attr_set = true; }
-    // split-K on small maps (12x40 .. 24x80: 60 .. 480 tiles with K = 2304 .. 4608): more workgroups, same gather work
-    int ksplit = 1;
-    if (d->workspace && g_opt_dcn_ksplit != 1 && d->Cout == d->Cout_pad) {
-        ksplit = g_opt_dcn_ksplit > 1 ? g_opt_dcn_ksplit : (tiles <= 256 ? 3 : 1);   // layer_bench: 512->256@12x40 83 -> 58 us, 256->64@24x80 49 -> 39; 480-tile layers lose
-        ksplit = std::min(ksplit, std::min(9, ep.nk / 4));
-        while (ksplit > 1 && ((ep.nk + ksplit - 1) / ksplit) * (ksplit - 1) >= ep.nk) --ksplit;
-        if ((size_t)ksplit * g.M * d->Cout_pad * sizeof(float) > (size_t)d->workspace_bytes) ksplit = 1;
-    }
+    const int ksplit = dcn_pick_ksplit(d, g.M, tiles, ep.nk);
     ++g_cnt_dcn_gather;
     if (ksplit > 1) {
         ep.ksplit = ksplit; ep.ws = reinterpret_cast<float*>(d->workspace); ep.ws_ld = d->Cout_pad;
@@ -543,12 +570,27 @@ static int launch_dcn(const mfx_dcn_desc* d, const DcnGeom& g, EpiArgs ep, hipSt
     MFX_HIP_CHECK(hipGetLastError());
     return MFX_OK;
 }
+// The tile of n same-shape modules launched as one grid (n = 1: a module alone).  N % 128 == 0: the 64x128 tile gathers every A row once where the
+// 64x64 tile gathers it N / 64 times, but needs a workgroup per CU -- counted over the whole GRID, so a group has the workgroups to fill the device
+// without split-K where a module alone has not (two 256 -> 128 @ 24x80 modules at B = 8: 2 x 240).  N == 64 has one N tile either way and nothing is
+// gathered twice: its rule counts one module's pixels whatever n (profiles/dcn_group.md).
+static int dcn_pick_tile(int M, int N, int n) {
+    int tile = N == 64 ? (cdiv(M, 128) >= 512 ? T_128x64 : T_64x64)
+                       : (N % 128 == 0 && (long)n * cdiv(M, 64) * (N / 128) >= 256 ? T_64x128 : T_64x64);
+    if (g_opt_dcn_tile && tile_fits(g_opt_dcn_tile, N)) tile = g_opt_dcn_tile;
+    return tile;
+}
+// would mfx_dcn_nhwc run this module, alone, split-K?  (The grouped launch has no split-K form: it leaves such modules to the one-module launches.)
+static bool dcn_alone_splits_k(const mfx_dcn_desc* d) {
+    const int M = d->B * d->Ho * d->Wo, N = d->Cout_pad, tile = dcn_pick_tile(M, N, 1);
+    const int bm = (tile == T_128x64 || tile == T_128x128) ? 128 : 64, bn = (tile == T_64x128 || tile == T_128x128) ? 128 : 64;
+    const int kc = (g_opt_kc != 4 && d->C >= 64) ? 8 : 4;      // (16-bit maps: 8 elements per 16-byte chunk)
+    return dcn_pick_ksplit(d, M, cdiv(M, bm) * (N / bn), d->K_pad / (kc * 8)) > 1;
+}
 template <typename T> static int dispatch_dcn(const mfx_dcn_desc* d, const DcnGeom& g, const EpiArgs& ep, hipStream_t st) {
     const int N = d->Cout_pad;
     if (N % 64 != 0) return mfx_fail(MFX_ERR_ARG, "dcn: Cout_pad must be a multiple of 64");
-    int tile = N == 64 ? (cdiv(g.M, 128) >= 512 ? T_128x64 : T_64x64)
-                       : (N % 128 == 0 && cdiv(g.M, 64) * (N / 128) >= 256 ? T_64x128 : T_64x64);
-    if (g_opt_dcn_tile && tile_fits(g_opt_dcn_tile, N)) tile = g_opt_dcn_tile;
+    const int tile = dcn_pick_tile(g.M, N, 1);
     const bool kc8 = g_opt_kc != 4 && d->C >= 8 * ElemTraits<T>::ELEMS;
     switch (tile) {
         case T_128x64: return kc8 ? launch_dcn<T, 128, 64, 4, 1, 8>(d, g, ep, st) : launch_dcn<T, 128, 64, 4, 1, 4>(d, g, ep, st);
@@ -557,7 +599,74 @@ template <typename T> static int dispatch_dcn(const mfx_dcn_desc* d, const DcnGe
         default: return kc8 ? launch_dcn<T, 64, 64, 2, 2, 8>(d, g, ep, st) : launch_dcn<T, 64, 64, 2, 2, 4>(d, g, ep, st);
     }
 }
+
+template <typename T, int BM, int BN, int WM, int WN, int KC>
+static int launch_dcn_group(const mfx_dcn_desc* d, int n, const DcnGeom& g, EpiArgs ep, hipStream_t st) {
+    ep.tiles_n = d[0].Cout_pad / BN;
+    ep.nk = d[0].K_pad / (KC * ElemTraits<T>::ELEMS);
+    DcnGroupPtrs gp;
+    gp.tiles_per = cdiv(g.M, BM) * ep.tiles_n;
+    for (int i = 0; i < kGroupMax; ++i) {                     // unused slots repeat module 0 (never indexed: the grid has n * tiles_per workgroups)
+        const mfx_dcn_desc& di = d[i < n ? i : 0];
+        gp.x[i] = di.x; gp.om[i] = di.offmask; gp.w[i] = di.w; gp.scale[i] = di.scale; gp.shift[i] = di.shift; gp.y[i] = di.y;
+    }
+    auto k = dcn_igemm_group_kernel<T, BM, BN, WM, WN, KC>;
+    constexpr int smem = TileSmem<BM, BN, KC>::bytes;
+    static bool attr_set = false;
+    if (!attr_set) { int rc = set_smem(k, smem); if (rc) return rc; attr_set = true; }
+    hipLaunchKernelGGL(k, dim3(gp.tiles_per * n), dim3(WM * WN * 64), smem, st, gp, g, ep);
+    MFX_HIP_CHECK(hipGetLastError());
+    return MFX_OK;
+}
+template <typename T> static int dispatch_dcn_group(const mfx_dcn_desc* d, int n, const DcnGeom& g, const EpiArgs& ep, hipStream_t st) {
+    const int N = d[0].Cout_pad;
+    const int tile = dcn_pick_tile(g.M, N, n);
+    const bool kc8 = g_opt_kc != 4 && d[0].C >= 8 * ElemTraits<T>::ELEMS;
+    switch (tile) {
+        case T_128x64: return kc8 ? launch_dcn_group<T, 128, 64, 4, 1, 8>(d, n, g, ep, st) : launch_dcn_group<T, 128, 64, 4, 1, 4>(d, n, g, ep, st);
+        case T_64x128: return kc8 ? launch_dcn_group<T, 64, 128, 2, 2, 8>(d, n, g, ep, st) : launch_dcn_group<T, 64, 128, 2, 2, 4>(d, n, g, ep, st);
+        case T_128x128: return kc8 ? launch_dcn_group<T, 128, 128, 2, 2, 8>(d, n, g, ep, st) : launch_dcn_group<T, 128, 128, 2, 2, 4>(d, n, g, ep, st);
+        default: return kc8 ? launch_dcn_group<T, 64, 64, 2, 2, 8>(d, n, g, ep, st) : launch_dcn_group<T, 64, 64, 2, 2, 4>(d, n, g, ep, st);
+    }
+}
 }  // namespace mfx
+
+// n DCN modules (offset/mask conv, then the gather kernel) of one shape as two launches.  Everything that is not same-shape 16-bit gather-kernel work is
+// refused with 1 BEFORE anything is launched: the caller then runs module by module.
+extern "C" int mfx_dcn_module_group(const mfx_conv_desc* off, const mfx_dcn_desc* dcn, int n, void* stream) {
+    if (!off || !dcn) return mfx_fail(MFX_ERR_ARG, "dcn_module_group: null pointer");
+    if (!g_opt_dcn_group || n < 1 || n > kGroupMax) return 1;
+    const mfx_dcn_desc& d0 = dcn[0];
+    if (d0.dtype != MFX_BF16 && d0.dtype != MFX_F16) return 1;
+    for (int i = 0; i < n; ++i) {
+        const mfx_dcn_desc& d = dcn[i];
+        if (!d.x || !d.w || !d.y || !d.offmask) return mfx_fail(MFX_ERR_ARG, "dcn_module_group: null pointer");
+        if (d.nonsquare || !is_pow2(d.C) || d.C < 32 || d.kh * d.kw > 9 || d.K_pad != d.kh * d.kw * d.C) return 1;
+        if (d.Cout % 8 != 0 || d.Cout > d.Cout_pad || d.Cout_pad % 64 != 0 || d.B <= 0 || d.Ho <= 0 || d.Wo <= 0) return 1;
+        if (d.dtype != d0.dtype || d.B != d0.B || d.H != d0.H || d.W != d0.W || d.C != d0.C || d.kh != d0.kh || d.kw != d0.kw || d.stride != d0.stride ||
+            d.pad != d0.pad || d.dil != d0.dil || d.Ho != d0.Ho || d.Wo != d0.Wo || d.Cout != d0.Cout || d.Cout_pad != d0.Cout_pad || d.K_pad != d0.K_pad ||
+            d.ldy != d0.ldy || d.act != d0.act) return 1;
+        if (dcn_lds_takes_16bit(&d) || dcn_patch_takes(&d) || dcn_wave_takes(&d)) return 1;      // layers mfx_dcn_nhwc gives to another kernel family
+        if (dcn_alone_splits_k(&d)) return 1;                  // small maps: the split-K launches have another K order (and are the faster form there)
+        // the module's own offset/mask conv: same input, its output is the gather kernel's offmask
+        if (off[i].x != d.x || off[i].y != (void*)d.offmask || off[i].ldy != 32 || off[i].B != d.B || off[i].Ho != d.Ho || off[i].Wo != d.Wo) return 1;
+    }
+    if ((size_t)d0.B * d0.H * d0.W * d0.C * 2 >= ((size_t)1 << 32)) return 1;
+    if ((long)n * cdiv(d0.B * d0.Ho * d0.Wo, 64) * (d0.Cout_pad / 64) >= (1l << 30)) return 1;
+    DcnGeom g;
+    g.H = d0.H; g.W = d0.W; g.C = d0.C; g.lgC = ilog2(d0.C); g.Ho = d0.Ho; g.Wo = d0.Wo; g.kh = d0.kh; g.kw = d0.kw;
+    g.inv_kw = (65536 + d0.kw - 1) / d0.kw; g.stride = d0.stride; g.pad = d0.pad; g.dil = d0.dil; g.M = d0.B * d0.Ho * d0.Wo;
+    g.stride_w = d0.stride; g.pad_w = d0.pad; g.dil_w = d0.dil;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int rc = try_conv_halo_group(off, n, st);               // 1: these offset convs are not grouped compile-time-geometry work -- nothing was launched
+    if (rc != MFX_OK) return rc;
+    EpiArgs ep;
+    ep.scale = nullptr; ep.shift = nullptr; ep.res = nullptr; ep.y = nullptr; ep.ldy = d0.ldy; ep.ldres = 0;
+    ep.Cout = d0.Cout; ep.act = d0.act; ep.K_pad = d0.K_pad; ep.nk = 0; ep.tiles_n = 1;
+    const int rg = d0.dtype == MFX_F16 ? dispatch_dcn_group<half_t>(dcn, n, g, ep, st) : dispatch_dcn_group<bf16_t>(dcn, n, g, ep, st);
+    if (rg == MFX_OK) ++g_cnt_dcn_group;
+    return rg;
+}
 
 static bool dcn_fuses_offset_conv(const mfx_dcn_desc* d) { return dcn_lds_fuses_offset_conv(d) || dcn_patch_fuses_offset_conv(d); }
 extern "C" int mfx_dcn_fuses_offset_conv(const mfx_dcn_desc* d) { return (d && d->x && dcn_fuses_offset_conv(d)) ? 1 : 0; }

@@ -751,6 +751,7 @@ static bool dcn_lds_auto(const mfx_dcn_desc* d) {
     if (g_opt_dcn_lds >= 2) return true;
     return d->C == 64 && (long)d->B * d->H * d->W >= 65536;
 }
+bool dcn_lds_takes_16bit(const mfx_dcn_desc* d) { return dcn_lds_auto(d); }
 bool dcn_lds_fuses_offset_conv(const mfx_dcn_desc* d) {
     return g_opt_dcn_fuse_off && d->off_w_frag_f16 && d->off_shift && d->C == 64 && dcn_lds_auto(d);
 }

@@ -432,12 +432,19 @@ bool dcn_patch_fuses_offset_conv(const mfx_dcn_desc* d) {
     return g_opt_dcn_fuse_off && !d->nonsquare && d->off_w_frag_f16 && d->off_shift && dcn_patch_auto(d);
 }
 
+// the test try_dcn_patch makes before it launches anything: true = it takes the layer (a forced variant, or the automatic choice below)
+bool dcn_patch_takes(const mfx_dcn_desc* d) {
+    if (g_opt_dcn_patch == 0 || !d->w_frag_f16 || (d->dtype != MFX_BF16 && d->dtype != MFX_F16)) return false;
+    if (d->dtype == MFX_F16 && g_opt_dcn_patch != 1 && g_opt_dcn_patch != 8) return false;      // fp16 maps: the production variant only
+    if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1 || d->dil != 1 || d->Ho != d->H || d->Wo != d->W) return false;
+    if (d->C % 64 != 0 || d->K_pad != 9 * d->C || d->Cout_pad % 64 != 0) return false;
+    if (g_opt_dcn_patch >= 2 && g_opt_dcn_patch <= 8) return true;
+    return d->C == 64 && d->Cout_pad == 64 && (long)d->B * d->H * d->W >= 65536;
+}
+
 // returns 1 if handled, 0 to fall through to the older kernels, < 0 on error
 int try_dcn_patch(const mfx_dcn_desc* d, hipStream_t st) {
-    if (g_opt_dcn_patch == 0 || !d->w_frag_f16 || (d->dtype != MFX_BF16 && d->dtype != MFX_F16)) return 0;
-    if (d->dtype == MFX_F16 && g_opt_dcn_patch != 1 && g_opt_dcn_patch != 8) return 0;      // fp16 maps: the production variant only
-    if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1 || d->dil != 1 || d->Ho != d->H || d->Wo != d->W) return 0;
-    if (d->C % 64 != 0 || d->K_pad != 9 * d->C || d->Cout_pad % 64 != 0) return 0;
+    if (!dcn_patch_takes(d)) return 0;
     const long px = (long)d->B * d->H * d->W;
     if (g_opt_dcn_patch >= 5 && g_opt_dcn_patch <= 7) {       // wide-margin variants: +-7 pixel offsets in range, 32-channel slices
         const int rc = g_opt_dcn_patch == 5 ? launch_dcn_patch<4, 4, 7, 32>(d, st)

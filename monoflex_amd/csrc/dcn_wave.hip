@@ -241,19 +241,25 @@ template <typename T> static int dcn_wave_variant(int v, const mfx_dcn_desc* d, 
     }
 }
 
+// the test try_dcn_wave makes before it launches anything: true = it takes the layer
+bool dcn_wave_takes(const mfx_dcn_desc* d) {
+    if (g_opt_dcn_wave == 0 || !d->w_frag) return false;
+    const int elems = (d->dtype == MFX_F32 || d->dtype == MFX_F16X2) ? 4 : 8;
+    if (d->C < 4 * elems || d->K_pad != d->kh * d->kw * d->C) return false;
+    const int N = d->Cout_pad;
+    if (N % 64 != 0) return false;
+    return !(g_opt_dcn_wave < 2 && (N % 128 != 0 || (d->B * d->Ho * d->Wo / 64) * (N / 128) < 512));
+}
+
 // returns 1 if handled, 0 to fall back to the first-generation kernel, < 0 on error
 int try_dcn_wave(const mfx_dcn_desc* d, hipStream_t st) {
-    if (g_opt_dcn_wave == 0 || !d->w_frag) return 0;
-    const int elems = (d->dtype == MFX_F32 || d->dtype == MFX_F16X2) ? 4 : 8;
-    if (d->C < 4 * elems || d->K_pad != d->kh * d->kw * d->C) return 0;
+    if (!dcn_wave_takes(d)) return 0;
     const int N = d->Cout_pad;
-    if (N % 64 != 0) return 0;
     const int bn[8] = {0, 64, 128, 128, 256, 256, 64, 128};
     // measured (tools/conv_probe.py, MI355X): every variant of both kernel generations lands within ~10 % -- the gather is
     // L1/texture-bandwidth bound (each input element is fetched ~36x; 64->64 @ B=8 moves 1.13 GB through L1 in 90 us =
     // 77 % of 64 B/clk/CU).  The 1-wave x 64-channel variant spills, so Cout = 64 stays on the first-generation kernel.
-    // Small maps (M/64 workgroups < 2 per CU) keep the first generation too: its 64x64 tiling has 2-4x more waves.
-    if (g_opt_dcn_wave < 2 && (N % 128 != 0 || (d->B * d->Ho * d->Wo / 64) * (N / 128) < 512)) return 0;
+    // Small maps (M/64 workgroups < 2 per CU) keep the first generation too: its 64x64 tiling has 2-4x more waves.  (That test: dcn_wave_takes.)
     int v = N % 256 == 0 ? 5 : N % 128 == 0 ? 3 : 6;
     if (g_opt_dcn_wave >= 2 && g_opt_dcn_wave - 1 <= 7 && N % bn[g_opt_dcn_wave - 1] == 0) v = g_opt_dcn_wave - 1;
     const int rc = d->dtype == MFX_F16X2 ? dcn_wave_variant<f32s_t>(v, d, st) : d->dtype == MFX_F32 ? dcn_wave_variant<float>(v, d, st)

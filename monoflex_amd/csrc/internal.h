@@ -26,6 +26,19 @@ bool dcn_patch_fuses_offset_conv(const mfx_dcn_desc* d);
 int try_dcn_lds(const mfx_dcn_desc* d, hipStream_t st);
 bool dcn_lds_fuses_offset_conv(const mfx_dcn_desc* d);
 
+// "would try_dcn_* take this layer?" without launching (the test each of them makes first; dcn_lds: the 16-bit modes only):
+// mfx_dcn_module_group leaves such layers to mfx_dcn_nhwc
+bool dcn_wave_takes(const mfx_dcn_desc* d);
+bool dcn_patch_takes(const mfx_dcn_desc* d);
+bool dcn_lds_takes_16bit(const mfx_dcn_desc* d);
+
+// Grouped launches (mfx_dcn_module_group, conv_kernels.hip): n <= kGroupMax layers of identical geometry and dtype in one grid.
+// conv_halo.hip: the grouped form of the fp32-out 3x3 kernel for the n offset/mask convs d[0..n), each with the variant try_conv_halo picks
+// for it alone: 0 = ran, 1 = not applicable (nothing launched; the caller launches conv by conv), < 0 = error.  conv_cw.hip owns the kernel.
+constexpr int kGroupMax = 4;
+int try_conv_halo_group(const mfx_conv_desc* d, int n, hipStream_t st);
+int try_conv_cw_group(const mfx_conv_desc* d, int n, int v, hipStream_t st);
+
 }  // namespace mfx
 
 // dcn_ext.hip: dst[b][cd0 + c][p] (+)= src[b][cs0 + c][p], c < Cg: a channel slice of an NCHW fp32 tensor (accumulate != 0: adds)

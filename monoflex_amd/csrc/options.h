@@ -36,6 +36,8 @@
     X(dcn_fuse_off, 1, MFX_NOLO, MFX_NOHI, "1 = the LDS-patch kernel computes the offset/mask conv itself where the caller supplies its weights") \
     X(dcn_lds, 1, MFX_NOLO, MFX_NOHI, "0 = off, 1 = automatic (64 -> 64 on large 16-bit maps), 2 = wherever the kernel applies") \
     X(dcn_lds_rows, 16, MFX_NOLO, MFX_NOHI, "tile rows, 16 | 8 (three workgroups per CU; measured slower: 2.570 vs 2.551 ms per step, profiles/r06_dcn_lds.md)") \
+    X(dcn_group, 1, 0, 1, "1 = mfx_dcn_module_group runs same-shape 16-bit gather-kernel DCN modules as one offset-conv launch and one gather launch " \
+        "(bit-identical output), 0 = it refuses every group and the caller launches module by module") \
     /* detection heads and decode (heads.hip, decode.hip) */ \
     X(heads_persist, 1, MFX_NOLO, MFX_NOHI, "1 = one workgroup per resident slot (n > 1: n workgroups), each a contiguous range of (tile, branch) units; " \
         "0 = one workgroup per tile.  B=8 bf16: 516 -> 503 us (tools/probes/heads_probe.py), bit-identical output") \
@@ -101,6 +103,8 @@
     X(dcn_patch, "launches of the third-generation, LDS-patch DCN kernel (dcn_patch.hip)") \
     X(dcn_wave, "launches of the second-generation DCN kernel (dcn_wave.hip)") \
     X(dcn_gather, "launches of the first-generation fused gather DCN kernel (conv_kernels.hip)") \
+    X(dcn_group, "calls of mfx_dcn_module_group that ran a group (two launches: the grouped offset/mask conv, the grouped gather kernel; " \
+        "neither is counted in conv_cw / dcn_gather)") \
     X(conv_cw, "launches of the compile-time-geometry 3x3 kernel (conv_cw.hip)") \
     X(conv_cws, "launches of its split-precision form (conv_cws.hip)") \
     X(conv_halo, "launches of the LDS-staged halo kernel (conv_halo.hip)") \

@@ -172,6 +172,7 @@ SYMBOLS = {
     "mfx_heads_fused": (_I, [ctypes.POINTER(HeadsDesc), _P]),
     "mfx_heads_fused_act": (_I, [ctypes.POINTER(HeadsDesc), _I, _P]),
     "mfx_dcn_fuses_offset_conv": (_I, [ctypes.POINTER(DcnDesc)]),
+    "mfx_dcn_module_group": (_I, [ctypes.POINTER(ConvDesc), ctypes.POINTER(DcnDesc), _I, _P]),
     "mfx_edge_scatter_add": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "mfx_edge_chain": (_I, [ctypes.POINTER(EdgeChainDesc), _P]),
     "mfx_edge_chain_act": (_I, [ctypes.POINTER(EdgeChainDesc), _I, _P]),

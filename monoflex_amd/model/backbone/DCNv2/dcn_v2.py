@@ -111,14 +111,14 @@ class DCN(DCNv2):
             self._packs[key] = p
         return self._packs[key]
 
-    def forward_nhwc(self, x, bn=None, act=L.ACT_NONE):
+    def forward_nhwc(self, x, bn=None, act=L.ACT_NONE, done=None):
         """x (B,H,W,C) NHWC; offset/mask conv (fp32 out, sigmoid on the 9 mask channels fused) then the
         fused gather+MFMA kernel with bias (+BN, +act) folded into its epilogue."""
         if OFFSET_CONV_FP32[0] and x.dtype != torch.float32:    # ablation switch (tools/bf16_ablation.py): offsets from fp32 operands
             offmask = ops.conv2d(x.float(), self.packed_offset(torch.float32), out_dtype=torch.float32)
         else:
             tag = ops.compute_tag(self, x.dtype)
-            return ops.dcn_module(x, self.packed_offset(tag), self.packed_main(tag, bn, act))[0]
+            return ops.dcn_module(x, self.packed_offset(tag), self.packed_main(tag, bn, act), done=done)[0]     # done: ops.dcn_module_group's result for this module
         return ops.dcn(x, offmask, self.packed_main(ops.compute_tag(self, x.dtype), bn, act))
 
     def forward_nhwc_train(self, x):

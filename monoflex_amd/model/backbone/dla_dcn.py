@@ -281,10 +281,10 @@ class DeformConv(nn.Module):
         self.actf = nn.Sequential(nn.BatchNorm2d(cho, momentum=BN_MOMENTUM), nn.ReLU(inplace=True))
         self.conv = DCN(chi, cho, kernel_size=(3, 3), stride=1, padding=1, dilation=1, deformable_groups=1)
 
-    def forward(self, x):                                      # NHWC; DCN + BN + ReLU in one kernel epilogue
+    def forward(self, x, done=None):                           # NHWC; DCN + BN + ReLU in one kernel epilogue
         if self.training:
             return AG.bn_act(self.conv.forward_nhwc_train(x), self.actf[0], L.ACT_RELU)
-        return self.conv.forward_nhwc(x, bn=self.actf[0], act=L.ACT_RELU)
+        return self.conv.forward_nhwc(x, bn=self.actf[0], act=L.ACT_RELU, done=done)     # done: (y, offmask) from IDAUp._grouped_proj
 
 
 class IDAUp(nn.Module):
@@ -302,18 +302,51 @@ class IDAUp(nn.Module):
         packs = self.__dict__.setdefault("_packs", {})
         if not self.training and PARALLEL_PROJ[0] and endp - startp > 2 and layers[startp].is_cuda:
             return self._forward_parallel_proj(layers, startp, endp, packs)
+        proj = {} if self.training else self._grouped_proj(layers, startp, endp)
         for i in range(startp + 1, endp):
             k = i - startp
             up = getattr(self, "up_" + str(k))
             if k not in packs:
                 packs[k] = ops.pack_upsample(up.weight)
-            t = getattr(self, "proj_" + str(k))(layers[i])
+            t = getattr(self, "proj_" + str(k))(layers[i], done=proj.pop(k)) if k in proj else getattr(self, "proj_" + str(k))(layers[i])
             if self.training:
                 t = AG.UpsampleAddFn.apply(t, up.weight, layers[i - 1], up.stride[0])
                 layers[i] = getattr(self, "node_" + str(k))(t)
                 continue
             t = ops.upsample_add(t, packs[k], up.stride[0], skip=layers[i - 1])      # up(proj(x_i)) + x_{i-1}
             layers[i] = getattr(self, "node_" + str(k))(t)
+
+
+def _idaup_grouped_proj(self, layers, startp, endp):
+    """Inference, 16-bit maps: proj_k(layers[startp + k]) reads only its own level's map, which nothing writes before iteration k, so the proj modules
+    of one IDAUp are independent of each other and of the node chain.  Those of equal shape (two 256 -> 128 in dla_up.ida_1, three 128 -> 64 in
+    dla_up.ida_2) are computed up front as one group -- one offset/mask conv launch and one gather launch on the current stream
+    (ops.dcn_module_group; bit-identical to the separate launches, which it falls back to where the library does not take the group).
+    -> {k: (y, offmask)} for the modules computed here; forward() hands each pair to its module (`done=`), which returns y through its own call
+    path, so every proj module is still entered as a module."""
+    from .DCNv2 import dcn_v2
+    out = {}
+    if endp - startp < 3 or dcn_v2.OFFSET_CONV_FP32[0] or not layers[startp + 1].is_cuda:
+        return out
+    groups = {}
+    for k in range(1, endp - startp):
+        x, m = layers[startp + k], getattr(self, "proj_" + str(k))
+        if x.dtype in (torch.bfloat16, torch.float16) and ops.compute_tag(m.conv, x.dtype) == x.dtype:
+            groups.setdefault((tuple(x.shape), x.dtype, m.conv.out_channels), []).append(k)
+    for ks in groups.values():
+        for j in range(0, len(ks) - 1, 4):
+            part = ks[j:j + 4]
+            if len(part) < 2:
+                continue
+            mods = [getattr(self, "proj_" + str(k)) for k in part]
+            xs = [layers[startp + k] for k in part]
+            ys, oms = ops.dcn_module_group(xs, [m.conv.packed_offset(x.dtype) for m, x in zip(mods, xs)],
+                                           [m.conv.packed_main(x.dtype, m.actf[0], L.ACT_RELU) for m, x in zip(mods, xs)])
+            out.update(zip(part, zip(ys, oms)))
+    return out
+
+
+IDAUp._grouped_proj = _idaup_grouped_proj
 
 
 def _idaup_forward_parallel_proj(self, layers, startp, endp, packs):

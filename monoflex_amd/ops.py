@@ -228,12 +228,17 @@ def dcn_ps(x, offmask, p: PackedConv):
 
 
 @on_tensor_device
-def dcn_module(x, p_off: PackedConv, p: PackedConv, need_offmask=False):
+def dcn_module(x, p_off: PackedConv, p: PackedConv, need_offmask=False, done=None):
     """The DCN module of the reference (dcn_v2.py:118-128): offset/mask conv (27 -> 32 channels, fp32 out, sigmoid on the mask channels)
     followed by the fused DCNv2.  Where the library's LDS-patch kernel takes the layer (mfx_dcn_fuses_offset_conv: 64 -> 64 on large
     16-bit maps) the offset conv runs INSIDE it -- one launch, the (B,H,W,32) offset map exists only if `need_offmask` (training: the
-    backward pass reads it).  -> (y, offmask or None)"""
+    backward pass reads it).  -> (y, offmask or None)
+    `done`: this module's (y, offmask) where `dcn_module_group` has computed it already with other modules of its shape -- returned as it is,
+    nothing is launched: the module is still entered through this function, so whoever wraps it (hooks, the layer-by-layer oracle walk of the
+    tests) sees every module's input, output and offset map."""
     _need_cuda(x)
+    if done is not None:
+        return done
     B, H, W, C = x.shape
     if p.stride == 1 and p.pad_h == 1 and p.kh == 3 and p.kw == 3:
         y = torch.empty((B, H, W, p.Cout), dtype=x.dtype, device=x.device)
@@ -246,6 +251,50 @@ def dcn_module(x, p_off: PackedConv, p: PackedConv, need_offmask=False):
     if dcn_ps_applies(x, p):
         return dcn_ps(x, om, p), om
     return dcn(x, om, p), om
+
+
+@on_tensor_device
+def dcn_module_group(xs, p_offs, ps):
+    """The DCN modules (xs[i], p_offs[i], ps[i]) -- independent of each other -- as one grouped offset/mask conv launch and one grouped gather launch
+    where the library takes them (mfx_dcn_module_group: 2..4 modules of identical shape on the 16-bit gather kernel; bit-identical to separate
+    launches), module by module through `dcn_module` otherwise.  -> ([y_i], [offmask_i or None])"""
+    _need_cuda(*xs)
+    n = len(xs)
+    x0, p0 = xs[0], ps[0]
+
+    def same(a, b):
+        return all(getattr(a, f) == getattr(b, f) for f in ("kh", "kw", "stride", "pad_h", "pad_w", "dil_w", "Ck", "Cout", "Cout_pad", "K_pad", "act", "split"))
+    ok = (1 <= n <= 4 and x0.dtype in (torch.bfloat16, torch.float16) and not p0.split and p0.stride == 1 and p0.pad_h == 1 and p0.kh == 3 and p0.kw == 3
+          and all(x.shape == x0.shape and x.dtype == x0.dtype and x.is_contiguous() for x in xs)
+          and all(same(p, p0) for p in ps) and all(same(q, p_offs[0]) for q in p_offs)
+          and all(q.w_frag is not None and q.Cout_pad == 32 for q in p_offs)
+          and not any(dcn_ps_applies(x, p) for x, p in zip(xs, ps)))          # project-then-sample layers are routed here, not in the library
+    if ok:
+        B, H, W, C = x0.shape
+        offs, dcns = (L.ConvDesc * n)(), (L.DcnDesc * n)()
+        ys = [torch.empty((B, H, W, p0.Cout), dtype=x0.dtype, device=x0.device) for _ in range(n)]
+        oms = [torch.empty((B, H, W, 32), dtype=torch.float32, device=x0.device) for _ in range(n)]
+        for i, (x, q, p) in enumerate(zip(xs, p_offs, ps)):
+            d = offs[i]
+            d.x, d.w, d.w_frag, d.y = x.data_ptr(), q.w.data_ptr(), q.w_frag.data_ptr(), oms[i].data_ptr()
+            d.scale = q.scale.data_ptr() if q.scale is not None else None
+            d.shift = q.shift.data_ptr() if q.shift is not None else None
+            d.B, d.H, d.W, d.x_pixstride, d.Ck = B, H, W, C, q.Ck
+            d.kh, d.kw, d.stride, d.pad_h, d.pad_w, d.dil_w = q.kh, q.kw, q.stride, q.pad_h, q.pad_w, q.dil_w
+            d.Ho, d.Wo, d.M, d.Cout, d.Cout_pad, d.K_pad = H, W, B * H * W, q.Cout, q.Cout_pad, q.K_pad
+            d.ldy, d.ldres, d.act, d.dtype, d.out_dtype = q.Cout, 0, q.act, _dt(x.dtype), L.MFX_F32
+            dd = _dcn_desc(x, oms[i], p, ys[i])
+            if B * H * W * p.Cout_pad <= SPLITK_MAX_ELEMS:       # as `dcn` does: a module that would run split-K alone is not grouped
+                ws = _splitk_workspace(x.device)
+                dd.workspace, dd.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+            ctypes.memmove(ctypes.byref(dcns[i]), ctypes.byref(dd), ctypes.sizeof(L.DcnDesc))
+        rc = L.load().mfx_dcn_module_group(offs, dcns, n, _stream())
+        if rc == 0:
+            return ys, oms
+        if rc < 0:
+            L.check(rc, "mfx_dcn_module_group")
+    outs = [dcn_module(x, q, p) for x, q, p in zip(xs, p_offs, ps)]             # not applicable (rc == 1): nothing was launched
+    return [o[0] for o in outs], [o[1] for o in outs]
 
 
 @on_tensor_device
