@@ -534,31 +534,52 @@ class HeadConvGatherFn(Function):
     (reference detector_predictor.py:125-147: the class / 3d_offset trunks feed both their head conv and the edge fusion).
     As two nodes the gather's gradient is a dense zero map of f's size (126 MB at B=8) with ~6.7k rows scattered into it, which
     autograd then adds to the conv's data gradient in another full pass; here the rows are added into the data gradient in place.
-    Returns (y with padded channels, rows [len(rowmap), C])."""
+    Returns (y with padded channels, rows [len(rowmap), C]).
+
+    Many rows can land on one pixel: every sequence position at or beyond edge_len[b] names pixel (0, 0) of image b (the padded edge_indices are
+    zeros), and the replicate halo repeats the end pixels.  Their gradients are summed per pixel in fp32 and added to the data gradient with ONE
+    more rounding of the activation type (`first`: edge_first_rows(rowmap, B), a function of the targets; built here when not given).  Added row
+    by row into the 16-bit map they rounded once per row, and an addend below half an ulp of the running value was lost entirely."""
 
     @staticmethod
-    def forward(ctx, f, weight, bias, rowmap):
+    def forward(ctx, f, weight, bias, rowmap, first=None):
         f = _c(f)
         Cout, Cin = weight.shape[0], weight.shape[1]
         cpad = _pad_channels(Cout, f.dtype)
         shift = _padded_bias(bias, ops.cout_pad(cpad)) if bias is not None else None
         y = ops.conv2d(f, _pack_weight(weight, f.dtype, 0, cpad, Cin, 1, 0, 0, shift), out_dtype=torch.float32)
         e = f.view(-1, Cin).index_select(0, rowmap)
-        ctx.save_for_backward(f, weight, rowmap)
+        ctx.save_for_backward(f, weight, rowmap, first)
         ctx.cfg = (bias is not None, Cout)
         return y, e
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy, de):
-        f, weight, rowmap = ctx.saved_tensors
+        f, weight, rowmap, first = ctx.saved_tensors
         has_bias, Cout = ctx.cfg
         needs = (True,) + tuple(ctx.needs_input_grad[1:3])       # the rows' gradient lands in dx
         dx, dw, db = _conv_backward(f, weight, dy, 1, 0, has_bias, Cout, needs)
         if not dx.is_contiguous():
             dx = dx.contiguous()
-        dx.view(-1, dx.shape[-1]).index_add_(0, rowmap, _c(de).to(dx.dtype))       # replicate-padded ends / padding rows repeat: atomics
-        return dx, dw, db, None
+        if first is None:
+            first = edge_first_rows(rowmap, f.shape[0])
+        rows = dx.view(-1, dx.shape[-1])
+        # per pixel: the fp32 sum of its rows, kept at the first position that names it (replicate-padded ends / padding rows repeat: atomics) ...
+        s = torch.zeros(de.shape, dtype=torch.float32, device=dx.device).index_add_(0, first, _c(de).float())
+        # ... then every position writes data gradient + sum, rounded once; the positions of one pixel write the same value
+        rows.index_copy_(0, rowmap, rows.index_select(0, rowmap).float().add_(s.index_select(0, first)).to(dx.dtype))
+        return dx, dw, db, None, None
+
+
+def edge_first_rows(rowmap, B):
+    """long [B Lp]: for every position of `rowmap` (image-major, Lp positions per image; pixel rows of different images differ) the smallest
+    position that names the same pixel.  Static shapes, no host sync, no atomics; a function of the targets only (predictor.edge_plan)."""
+    rm = rowmap.view(B, -1)
+    Lp = rm.shape[1]
+    pos = torch.arange(Lp, dtype=torch.int32, device=rm.device)
+    first = torch.where(rm.unsqueeze(2) == rm.unsqueeze(1), pos.view(1, 1, Lp), pos.new_full((), Lp)).amin(dim=2).long()     # (B Lp^2 int32, once per batch)
+    return (first + torch.arange(B, device=rm.device).view(B, 1) * Lp).reshape(-1)
 
 
 @_device_guarded
@@ -999,6 +1020,7 @@ class FanOutConvFn(Function):
     @staticmethod
     def forward(ctx, x, pad, *weights):
         x = _c(x)
+        ctx.set_materialize_grads(False)                       # an unused output arrives as dy = None (not as a zero map to convolve)
         ys = []
         for w in weights:
             Cout, Cin = w.shape[0], w.shape[1]

@@ -245,6 +245,7 @@ class _predictor(nn.Module):
                 if plan is None:
                     plan = self.edge_plan(edge_indices, edge_lens, None, H, W)
                 rowmap, rows_center, valid_l = plan["rowmap"], plan["rows_center"], plan["valid_l"]
+                first = plan.get("first")                    # (a plan from before `first`: the node builds it)
         for bi, (t, heads) in enumerate(zip(trunks, lasts)):
             w = heads[0].weight if len(heads) == 1 else torch.cat([h.weight for h in heads], 0)
             b = heads[0].bias if len(heads) == 1 else torch.cat([h.bias for h in heads], 0)
@@ -257,7 +258,7 @@ class _predictor(nn.Module):
             feats.append(f)
             if fuse_nodes and (bi == 0 or bi - 1 == oi):
                 # head conv + gather of the trunk's rows at the edge pixels in one node (one data gradient for f)
-                yo, er = AG.HeadConvGatherFn.apply(f, w, b, rowmap)
+                yo, er = AG.HeadConvGatherFn.apply(f, w, b, rowmap, first)
                 outs.append(yo if yo.shape[-1] == w.shape[0] else yo[..., :w.shape[0]])
                 edge_rows[bi] = er
             else:
@@ -345,12 +346,13 @@ class _predictor(nn.Module):
     def edge_plan(self, edge_indices, edge_lens, object_rows=None, H=None, W=None):
         """The edge fusion's index tensors, functions of the targets only (static shapes, no host sync): `rowmap` long [B (L + 2 h)] pixel rows of
         the sequence positions -h .. L - 1 + h (replicate padding, h = k // 2 = `edge_halo`), `rows_center` [B L] the positions 0 .. L - 1, `valid_l` float [B, L, 1] =
-        (l < edge_len[b]); with the loss's object table also `e_idx` / `hit` (`edge_plan_rows`)."""
+        (l < edge_len[b]), `first` long [B (L + 2 h)] the first position of `rowmap` naming the same pixel (HeadConvGatherFn sums the row gradients of a
+        pixel there); with the loss's object table also `e_idx` / `hit` (`edge_plan_rows`)."""
         H, W = H or self.output_height, W or self.output_width
         B, Lm = edge_indices.shape[0], edge_indices.shape[1]
         h = self.edge_halo
         rm = make_edge_rowmap(edge_indices, H, W, h).long()
-        plan = {"rowmap": rm, "rows_center": rm.view(B, Lm + 2 * h)[:, h:Lm + h].reshape(-1).contiguous(),
+        plan = {"rowmap": rm, "first": AG.edge_first_rows(rm, B), "rows_center": rm.view(B, Lm + 2 * h)[:, h:Lm + h].reshape(-1).contiguous(),
                 "valid_l": (torch.arange(Lm, device=rm.device).view(1, Lm) < edge_lens.view(B, 1)).float().unsqueeze(-1)}
         if object_rows is not None:
             plan.update(self.edge_plan_rows(object_rows, plan["rows_center"], plan["valid_l"], B, H, W))

@@ -111,6 +111,25 @@ def test_head_conv_gather_node_matches_two_nodes(cpu_ops):
         assert torch.allclose(g, h, atol=1e-4), float((g - h).abs().max())
 
 
+@pytest.mark.parametrize("halo", [0, 1, 3])
+def test_edge_first_rows_matches_a_python_loop(halo):
+    """autograd.edge_first_rows (where HeadConvGatherFn sums the row gradients of one pixel): the smallest position naming the same pixel, for
+    images without edge points, with the whole border and with a few points; int32 and int64 row maps alike."""
+    B, H, W, L = 3, 6, 10, 40
+    border = [(x, 0) for x in range(W)] + [(W - 1, y) for y in range(1, H)] + [(x, H - 1) for x in range(W - 1)] + [(0, y) for y in range(1, H - 1)]
+    ei = torch.zeros(B, L, 2, dtype=torch.int32)
+    ei[1, :len(border)] = torch.tensor(border, dtype=torch.int32)
+    ei[2, :7] = torch.tensor(border[5:12], dtype=torch.int32)
+    rm = make_edge_rowmap(ei, H, W, halo)
+    seen, want = {}, []
+    for j, p in enumerate(rm.tolist()):
+        want.append(seen.setdefault(p, j))
+    for r in (rm, rm.long()):
+        first = AG.edge_first_rows(r, B)
+        assert first.dtype == torch.int64 and first.tolist() == want
+    assert want[:L + 2 * halo] == [0] * (L + 2 * halo) and len(set(want)) == 1 + (28 + 1 - 1) + (7 + 1)
+
+
 def test_padded_bias_registry_follows_the_parameter():
     """autograd._padded_bias: persistent zero-padded copy of a bias parameter -- same buffer every step, refreshed when the
     parameter's version moves (on demand) or by pack_all_weights() (one _foreach_copy_), dropped with the parameter."""

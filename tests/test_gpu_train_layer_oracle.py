@@ -34,8 +34,9 @@ the biased variance, (d) AdamW with L2 instead of decoupled weight decay.
 
 Not restated here, only counted (calls and dispatch families): the heads' fused nodes (FanOutConvFn, HeadConvGatherFn, EdgeScatterAddFn,
 GramRegHeadsHipFn) and the fused focal / object losses; so neither is the gradient they hand the backbone's output, nor p.grad of the parameters they
-consume.  GramRegHeadsHipFn has its own float64 reference at small shapes: tests/test_gpu_gram_heads_oracle.py (tests/gram_heads_ref.py); the other fused
-head nodes stay counted only -- they are made of kernels that are pinned exactly."""
+consume.  GramRegHeadsHipFn has its own float64 reference at small shapes: tests/test_gpu_gram_heads_oracle.py (tests/gram_heads_ref.py); so have
+FanOutConvFn, HeadConvGatherFn and EdgeScatterAddFn: tests/test_gpu_head_nodes.py (tests/head_nodes_ref.py), with derived bounds at the production
+channel counts."""
 import json
 import os
 import time
