@@ -133,7 +133,8 @@ template <> struct Raw8<float> {
 // List entries.  fp32 maps keep (sample, fp32 weight) pairs: 8 bytes, 47 per pixel in the 48 KB that leave three workgroups
 // per CU.  bf16 maps pack the sample as window coordinates (5 + 5 bits) + tap (4) and the weight's exponent and top ten
 // mantissa bits (18 bits, the weight is non-negative; 2^-11 relative: below the bf16 operands it multiplies, at the rounding of fp16 ones) into 4 bytes:
-// 94 per pixel, so a list practically never overflows (mean 36 entries, sigma ~6) and the far path is left to far offsets.
+// BT_LCAP_BF16 = 62 per pixel (mean 36 entries, sigma ~6: about four sigma), so a list rarely overflows; an entry beyond the capacity takes the
+// far path, which is exact (tests/test_gpu_dcn_bwd_edges.py fills lists past 62 on purpose).
 template <typename T> struct BtEntry {        // 16-bit activations
     typedef uint32_t type;
     static constexpr int LCAP = BT_LCAP_BF16;
