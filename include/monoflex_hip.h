@@ -973,6 +973,25 @@ int mfx_kitti_eval_thresholds(const mfx_kitti_eval_desc* d, const double* sorted
 /* 4: matching at every threshold with false-positive / DontCare / orientation accounting -> pr (eval.py:289-326). */
 int mfx_kitti_eval_match_pass2(const mfx_kitti_eval_desc* d, void* stream);
 
+/* The detections of a whole pass -> the `dt` / `dt_off` / `pair_off` inputs above, without result files (TEST.EVAL_ON_DEVICE,
+ * monoflex_amd/data/evaluation.py).  The pass leaves its decode rows on the device:
+ *   det   (N, NM, K, 14) fp32  [cls, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, score]   (mfx_decode_boxes*; NM depth methods, 1 for a plain pass)
+ *   valid (N, NM, K) int32     non-zero = the slot is a detection
+ * row i being the image whose detections the evaluator pairs with ground-truth image i.  K <= MFX_EVAL_MAX_DET, or MFX_ERR_ARG.
+ * A record is exactly what parsing the result file of the row gives (csrc/kitti_eval_pack_math.h: every value rounded to four
+ * decimals in fp32 as numpy does, multiply / rint / divide, then widened; h, w, l -> l, h, w; truncated = occluded = 0), and the
+ * records of an image keep the slot order, which is the file's line order.  Two launches, one wave per image:
+ *   count: n_det[i] = number of valid slots of (i, m), n_pair[i] = n_det[i] * (gt_off[i+1] - gt_off[i]);
+ *   rows : with dt_off (N+1) = the exclusive scan of n_det (the caller scans: any device scan), slot k of image i writes its
+ *          record at row dt_off[i] + (number of valid slots below k).  `dt` needs room for dt_off[N] records; N * K always do.
+ * pair_off is the exclusive scan of n_pair.  The method index travels beside the buffers; mfx_kitti_eval_desc and
+ * MFX_ABI_VERSION are unchanged. */
+#define MFX_EVAL_DET_ROW 14
+int mfx_kitti_eval_pack_count(const int32_t* valid, int N, int NM, int K, int m, const int32_t* gt_off, int32_t* n_det,
+                              int64_t* n_pair, void* stream);
+int mfx_kitti_eval_pack_rows(const float* det, const int32_t* valid, int N, int NM, int K, int m, const int32_t* dt_off,
+                             double* dt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

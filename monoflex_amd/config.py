@@ -155,6 +155,9 @@ def _defaults():
         # declared by the reference (config/defaults.py) and read by none of its files; here USE_NMS '2d' / '3d' suppresses duplicate
         # detections on the device (ops.box_nms).  EVAL_DEPTH_METHODS is accepted and, as there, never read.
         USE_NMS='none', NMS_THRESH=-1., NMS_CLASS_AGNOSTIC=False, EVAL_DEPTH_METHODS=[],
+        # build-specific: score a validation pass from the rows it left on the device -- no result files are written or read back
+        # (engine/inference.py `eval_on_device`).  The file path stays the default: a KITTI submission needs the files.
+        EVAL_ON_DEVICE=False,
     ))
     C.OUTPUT_DIR = "./tools/logs"
     C.SEED = -1

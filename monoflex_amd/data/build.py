@@ -63,9 +63,15 @@ def make_data_loader(cfg, is_train=True):
 
 
 def build_test_loader(cfg, is_train=False):
+    """One loader per dataset of DATASETS.TEST.  Each carries `eval_on_device` = TEST.EVAL_ON_DEVICE: `run_test` hands its loaders to
+    engine.inference.inference / inference_all_depths without the config, and they read the switch there."""
     resident = _resident(cfg)
     if resident is not None:                                    # the store covers this rank's shard of the split
-        return [ResidentLoader(ds, batch_size=cfg.TEST.IMS_PER_BATCH, sampler=InferenceSampler(len(ds)), **resident)
-                for ds in build_dataset(cfg, is_train)]
-    return [DeviceLoader(ds, batch_size=cfg.TEST.IMS_PER_BATCH, sampler=InferenceSampler(len(ds)), num_workers=_workers(cfg))
-            for ds in build_dataset(cfg, is_train)]
+        loaders = [ResidentLoader(ds, batch_size=cfg.TEST.IMS_PER_BATCH, sampler=InferenceSampler(len(ds)), **resident)
+                   for ds in build_dataset(cfg, is_train)]
+    else:
+        loaders = [DeviceLoader(ds, batch_size=cfg.TEST.IMS_PER_BATCH, sampler=InferenceSampler(len(ds)), num_workers=_workers(cfg))
+                   for ds in build_dataset(cfg, is_train)]
+    for loader in loaders:
+        loader.eval_on_device = bool(cfg.get("TEST", {}).get("EVAL_ON_DEVICE", False))
+    return loaders

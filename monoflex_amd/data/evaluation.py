@@ -6,7 +6,11 @@ Same entry points as the reference -- `generate_kitti_3d_detection(prediction, p
 the work split differently: the host parses text and formats the report; the overlap matrices (2D, rotated BEV, 3D), the
 per-class / per-difficulty ignore rules, the greedy matching at every one of the <= 41 score thresholds and the PR
 accumulation run on the GPU (C ABI group 5, csrc/kitti_eval.hip), all images and all 54 (class, difficulty, metric, overlap
-set) combinations at once.  The reference does this with numba CPU loops plus a numba.cuda kernel for the rotated IoU."""
+set) combinations at once.  The reference does this with numba CPU loops plus a numba.cuda kernel for the rotated IoU.
+
+A second, opt-in path (TEST.EVAL_ON_DEVICE) skips the text: `DeviceResults` keeps the decode rows of a whole pass on the device,
+mfx_kitti_eval_pack_* (csrc/kitti_eval_pack.hip) turn them into the record table the result files would have parsed to, bit for bit,
+and `results_from_device` evaluates them against a `LabelTable` that was read once: the same report text and result dict, no files."""
 import ctypes
 import os
 import re
@@ -91,16 +95,13 @@ def pack_eval_inputs(gts, dts, classes, min_overlaps):
     return arrays, sizes, aos
 
 
-def pr_table(gts, dts, classes, min_overlaps, device="cuda"):
-    """[ (n_i,16) ] ground truths and detections, class codes, min_overlaps (num_k, 3, num_classes) ->
-    (pr (nc,3,3,nk,41,4) float64, num_thresholds (nc,3,3,nk), overlaps (3,n_pairs), pair offsets, compute_aos)."""
-    if torch.device(device).type != "cuda":
-        raise RuntimeError("the KITTI evaluator runs on the GPU (HIP kernels); there is no CPU fallback")
-    arrays, sz, aos = pack_eval_inputs(gts, dts, classes, min_overlaps)
+def _launch_pr(dev, sz, aos, device):
+    """The four evaluator launches on inputs that are already on the device: `dev` holds gt, dt, gt_off, dt_off, pair_off, classes and
+    min_overlaps as tensors (gt / dt may be absent or empty when there is no record), `sz` the sizes of pack_eval_inputs.
+    -> (pr (n_comb,41,4), num_thresholds (n_comb), overlaps (3, max(n_pairs,1))) device tensors; nothing here waits for the device."""
     B, n_gt, n_dt, n_pairs, nc, nk = sz["B"], sz["n_gt"], sz["n_dt"], sz["n_pairs"], sz["num_classes"], sz["num_k"]
     n_comb = nc * 9 * nk
     lib = L.load()
-    dev = _upload({k: v for k, v in arrays.items() if v.size}, device)
     f64 = dict(dtype=torch.float64, device=device)
     overlaps = torch.empty((3, max(n_pairs, 1)), **f64)
     tp_scores = torch.empty((n_comb, max(n_gt, 1)), **f64)
@@ -109,8 +110,8 @@ def pr_table(gts, dts, classes, min_overlaps, device="cuda"):
     num_valid = torch.empty((nc, 3), dtype=torch.int32, device=device)
     num_th = torch.empty(n_comb, dtype=torch.int32, device=device)
     d = L.KittiEvalDesc()
-    for k in arrays:
-        setattr(d, k, dev[k].data_ptr() if k in dev else None)
+    for k in ("gt", "dt", "gt_off", "dt_off", "pair_off", "classes", "min_overlaps"):
+        setattr(d, k, dev[k].data_ptr() if k in dev and dev[k].numel() else None)
     d.overlaps, d.tp_scores, d.thresholds, d.pr = overlaps.data_ptr(), tp_scores.data_ptr(), thresholds.data_ptr(), pr.data_ptr()
     d.num_valid_gt, d.num_thresholds = num_valid.data_ptr(), num_th.data_ptr()
     d.B, d.n_gt, d.n_dt, d.num_classes, d.num_k, d.compute_aos, d.n_pairs = B, n_gt, n_dt, nc, nk, int(aos), n_pairs
@@ -121,8 +122,19 @@ def pr_table(gts, dts, classes, min_overlaps, device="cuda"):
         ordered = torch.sort(tp_scores, dim=1, descending=True).values.contiguous()
         L.check(lib.mfx_kitti_eval_thresholds(ctypes.byref(d), ordered.data_ptr(), st), "mfx_kitti_eval_thresholds")
         L.check(lib.mfx_kitti_eval_match_pass2(ctypes.byref(d), st), "mfx_kitti_eval_match_pass2")
-    shape = (nc, 3, 3, nk)
-    return (pr.cpu().numpy().reshape(shape + (PTS, 4)), num_th.cpu().numpy().reshape(shape), overlaps[:, :n_pairs].cpu().numpy(),
+    return pr, num_th, overlaps
+
+
+def pr_table(gts, dts, classes, min_overlaps, device="cuda"):
+    """[ (n_i,16) ] ground truths and detections, class codes, min_overlaps (num_k, 3, num_classes) ->
+    (pr (nc,3,3,nk,41,4) float64, num_thresholds (nc,3,3,nk), overlaps (3,n_pairs), pair offsets, compute_aos)."""
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("the KITTI evaluator runs on the GPU (HIP kernels); there is no CPU fallback")
+    arrays, sz, aos = pack_eval_inputs(gts, dts, classes, min_overlaps)
+    dev = _upload({k: v for k, v in arrays.items() if v.size}, device)
+    pr, num_th, overlaps = _launch_pr(dev, sz, aos, device)
+    shape = (sz["num_classes"], 3, 3, sz["num_k"])
+    return (pr.cpu().numpy().reshape(shape + (PTS, 4)), num_th.cpu().numpy().reshape(shape), overlaps[:, :sz["n_pairs"]].cpu().numpy(),
             arrays["pair_off"], aos)
 
 
@@ -149,18 +161,22 @@ def _ap(curve, metric):
     return total / (40 if metric == "R40" else 11) * 100
 
 
-def get_official_eval_result(gts, dts, current_classes, metric="R40", device="cuda"):
-    """eval.py:648-741: (report text, {'Car_3d_0.70/moderate': AP, ...}) from record lists."""
+def _class_overlaps(current_classes):
+    """Class names or codes -> (codes, min_overlaps (2, 3, num_classes)): the strict and the loose overlap set (eval.py:650-660)."""
     name_to_class = {v: k for k, v in CLASS_TO_NAME.items()}
     if not isinstance(current_classes, (list, tuple)):
         current_classes = [current_classes]
     classes = [name_to_class[c] if isinstance(c, str) else int(c) for c in current_classes]
-    if metric not in ("R40", "R11"):
-        raise ValueError(metric)
     strict = np.array([[0.7, 0.5, 0.5, 0.7, 0.5, 0.7]] * 3)
     loose = np.array([[0.7, 0.5, 0.5, 0.7, 0.5, 0.5], [0.5, 0.25, 0.25, 0.5, 0.25, 0.5], [0.5, 0.25, 0.25, 0.5, 0.25, 0.5]])
-    mo = np.stack([strict, loose], axis=0)[:, :, classes]
-    pr, num_th, _, _, aos = pr_table(gts, dts, classes, mo, device)
+    return classes, np.stack([strict, loose], axis=0)[:, :, classes]
+
+
+def _report(pr, num_th, aos, classes, mo, metric):
+    """PR table -> (report text, result dict) under one metric (eval.py:662-741).  The table does not depend on the metric: 'R40' and
+    'R11' sample the same curves at different recall positions."""
+    if metric not in ("R40", "R11"):
+        raise ValueError(metric)
     prec, ori = _curves(pr, num_th)
     ap = _ap(prec, metric)                                          # [class, level, metric, k]
     ap_aos = _ap(ori[:, :, 0], metric) if aos else None
@@ -183,6 +199,15 @@ def get_official_eval_result(gts, dts, current_classes, metric="R40", device="cu
     return text, ret
 
 
+def get_official_eval_result(gts, dts, current_classes, metric="R40", device="cuda"):
+    """eval.py:648-741: (report text, {'Car_3d_0.70/moderate': AP, ...}) from record lists."""
+    classes, mo = _class_overlaps(current_classes)
+    if metric not in ("R40", "R11"):
+        raise ValueError(metric)
+    pr, num_th, _, _, aos = pr_table(gts, dts, classes, mo, device)
+    return _report(pr, num_th, aos, classes, mo, metric)
+
+
 def evaluate_python(label_path, result_path, label_split_file, current_class, metric="R40", score_thresh=-1, device="cuda"):
     """data/datasets/evaluation/__init__.py:31-34 -> evaluate.py:17-32. `score_thresh` > 0 drops detections scoring below it
     before the evaluation (kitti_common.py:191-202)."""
@@ -193,3 +218,142 @@ def evaluate_python(label_path, result_path, label_split_file, current_class, me
         dts = [d[d[:, 15] >= score_thresh] for d in dts]
     gts = read_label_folder(label_path, ids)
     return get_official_eval_result(gts, dts, current_class, metric=metric, device=device)
+
+
+# ---- evaluation of a pass that stayed on the device (TEST.EVAL_ON_DEVICE) -------------------------------------------------------------
+class LabelTable:
+    """The ground truths of a split as the evaluator reads them: `gt` (n_gt,16) = read_label_folder(label_dir, ids) concatenated and
+    `gt_off` (N+1), ids in split-file order as evaluate_python reads them.  Built once per dataset (LabelTable.of caches it there) and
+    uploaded once per device.  `row_of(image_id)`: the result folder is read back SORTED (read_label_folder) and paired with the ground
+    truths by position, so the detections of an image belong in the row that is the rank of its id among the split's ids."""
+
+    def __init__(self, label_dir, imageset_txt):
+        with open(imageset_txt) as f:
+            self.ids = [int(line) for line in f.readlines()]
+        gts = read_label_folder(label_dir, self.ids)
+        self.gt = np.concatenate(list(gts) + [np.zeros((0, REC))])
+        self.gt_off = np.concatenate([[0], np.cumsum([len(g) for g in gts])]).astype(np.int32)
+        self._rank = {idx: r for r, idx in enumerate(sorted(set(self.ids)))}
+        self._dev = {}
+
+    def __len__(self):
+        return len(self.ids)
+
+    @classmethod
+    def of(cls, dataset):
+        """The table of a dataset's split; the test split has no label files, which is a ValueError."""
+        if getattr(dataset, "split", None) == "test":
+            raise ValueError("the evaluation on the device reads the labels of the split, and the test split has none "
+                             "(TEST.EVAL_ON_DEVICE needs a validation split)")
+        table = getattr(dataset, "_label_table", None)
+        if table is None:
+            table = dataset._label_table = cls(dataset.label_dir, dataset.imageset_txt)
+        return table
+
+    def row_of(self, image_id):
+        try:
+            return self._rank[int(image_id)]
+        except KeyError:
+            raise ValueError("need one detection record array per ground-truth image (image %s is not in the split)" % (image_id,)) from None
+
+    def on(self, device):
+        """{gt, gt_off} on `device`, uploaded at the first call."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._dev:
+            self._dev[device] = dict(gt=torch.from_numpy(self.gt).to(device), gt_off=torch.from_numpy(self.gt_off).to(device))
+        return self._dev[device]
+
+
+def _check_slots(K):
+    if K > MAX_DET:
+        raise ValueError("at most %d detections per image (got %d)" % (MAX_DET, K))
+
+
+class DeviceResults:
+    """The detections of one pass, kept on the device: det (N, NM, K, 14) float32 and valid (N, NM, K) int32, row = LabelTable.row_of(id).
+    `scatter` files a batch by row (an image delivered twice overwrites its row, as its result file would be overwritten); `evaluate`
+    refuses a pass that left an image of the split out with the ValueError the file path raises on the count mismatch."""
+
+    def __init__(self, label_table, num_methods=1, K=50, device="cuda"):
+        _check_slots(K)
+        self.table, N = label_table, len(label_table)
+        self.det = torch.empty((N, num_methods, K, 14), dtype=torch.float32, device=device)
+        self.valid = torch.zeros((N, num_methods, K), dtype=torch.int32, device=device)
+        self.seen = np.zeros(N, dtype=bool)
+
+    def scatter(self, image_ids, det, valid):
+        """det (B,[NM,]K,14), valid (B,[NM,]K) of the images `image_ids` -> their rows; the row indices go up as one small pinned copy."""
+        rows = np.asarray([self.table.row_of(i) for i in image_ids], dtype=np.int64)
+        if tuple(det.shape[-2:]) != tuple(self.det.shape[-2:]) or det.numel() != len(rows) * self.det[0].numel() or valid.numel() != len(rows) * self.valid[0].numel():
+            raise ValueError("a batch of %d images brings det %s / valid %s, the buffer holds %s per image"
+                             % (len(rows), tuple(det.shape), tuple(valid.shape), tuple(self.det.shape[1:])))
+        index = _upload(dict(rows=rows), self.det.device)["rows"] if self.det.device.type == "cuda" else torch.from_numpy(rows)
+        self.det.index_copy_(0, index, det.reshape((len(rows),) + tuple(self.det.shape[1:])))
+        self.valid.index_copy_(0, index, valid.reshape((len(rows),) + tuple(self.valid.shape[1:])))
+        self.seen[rows] = True
+
+    def check_complete(self):
+        if not self.seen.all():
+            raise ValueError("need one detection record array per ground-truth image (%d of the split's %d images were not delivered)"
+                             % (int((~self.seen).sum()), len(self.seen)))
+
+    def evaluate(self, classes, metrics=("R40",), method=0):
+        self.check_complete()
+        return results_from_device(self.table, self.det, self.valid, classes, metrics, method)
+
+
+def pack_detections(gt_off, det, valid, method=0):
+    """det (N,NM,K,14) float32, valid (N,NM,K) int32 and the ground-truth offsets (N+1) int32, all on the device -> the evaluator's detection
+    inputs for depth method `method`: (dt (N*K,16) float64 of which the first n_dt rows are records, dt_off (N+1) int32, pair_off (N+1) int64,
+    n_dt, n_pairs, compute_aos).  Two launches (mfx_kitti_eval_pack_count / _rows) with two cumsums between them; n_dt, n_pairs and the first
+    record's alpha (eval.py:676-681: alpha == -10 marks "no orientation") come to the host in one small copy, the only wait."""
+    N, NM, K = (int(v) for v in valid.shape)
+    _check_slots(K)
+    if det.device.type != "cuda":
+        raise RuntimeError("the KITTI evaluator runs on the GPU (HIP kernels); there is no CPU fallback")
+    if tuple(det.shape) != (N, NM, K, 14) or det.dtype != torch.float32 or valid.dtype != torch.int32 or not (det.is_contiguous() and valid.is_contiguous()):
+        raise ValueError("pack_detections: det (N,NM,K,14) float32 and valid (N,NM,K) int32, contiguous; got %s %s / %s %s"
+                         % (tuple(det.shape), det.dtype, tuple(valid.shape), valid.dtype))
+    if tuple(gt_off.shape) != (N + 1,) or gt_off.dtype != torch.int32 or not 0 <= method < NM:
+        raise ValueError("pack_detections: gt_off (N+1) int32 and a method index below NM")
+    device, lib = det.device, L.load()
+    n_det = torch.empty(N, dtype=torch.int32, device=device)
+    n_pair = torch.empty(N, dtype=torch.int64, device=device)
+    dt_off = torch.zeros(N + 1, dtype=torch.int32, device=device)
+    pair_off = torch.zeros(N + 1, dtype=torch.int64, device=device)
+    dt = torch.empty((N * K, REC), dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        L.check(lib.mfx_kitti_eval_pack_count(valid.data_ptr(), N, NM, K, method, gt_off.data_ptr(), n_det.data_ptr(), n_pair.data_ptr(), st),
+                "mfx_kitti_eval_pack_count")
+        torch.cumsum(n_det, 0, dtype=torch.int32, out=dt_off[1:])
+        torch.cumsum(n_pair, 0, out=pair_off[1:])
+        L.check(lib.mfx_kitti_eval_pack_rows(det.data_ptr(), valid.data_ptr(), N, NM, K, method, dt_off.data_ptr(), dt.data_ptr(), st),
+                "mfx_kitti_eval_pack_rows")
+        head = torch.stack([dt_off[N].double(), pair_off[N].double(), dt[0, 3]]).cpu()
+    n_dt, n_pairs = int(head[0]), int(head[1])
+    return dt, dt_off, pair_off, n_dt, n_pairs, bool(n_dt > 0 and float(head[2]) != -10)
+
+
+def results_from_device(label_table, det, valid, classes, metrics=("R40",), method=0):
+    """[(report text, result dict) per metric] of the detections det / valid (pack_detections' layout, rows in LabelTable.row_of order)
+    against the split's labels: what evaluate_python returns for the result files of the same rows.  ONE PR table serves every metric."""
+    metrics = list(metrics)
+    for metric in metrics:
+        if metric not in ("R40", "R11"):
+            raise ValueError(metric)
+    if valid.shape[0] != len(label_table):
+        raise ValueError("need one detection record array per ground-truth image")
+    codes, mo = _class_overlaps(classes)
+    device = det.device
+    gt = label_table.on(device)
+    dt, dt_off, pair_off, n_dt, n_pairs, aos = pack_detections(gt["gt_off"], det, valid, method)
+    dev = _upload(dict(classes=np.asarray(codes, dtype=np.int32), min_overlaps=np.ascontiguousarray(mo, dtype=np.float64)), device)
+    dev.update(gt=gt["gt"], gt_off=gt["gt_off"], dt=dt, dt_off=dt_off, pair_off=pair_off)
+    sz = dict(B=len(label_table), n_gt=int(label_table.gt_off[-1]), n_dt=n_dt, n_pairs=n_pairs, num_classes=len(codes), num_k=int(mo.shape[0]))
+    pr, num_th, _ = _launch_pr(dev, sz, aos, device)
+    shape = (len(codes), 3, 3, int(mo.shape[0]))
+    pr, num_th = pr.cpu().numpy().reshape(shape + (PTS, 4)), num_th.cpu().numpy().reshape(shape)
+    return [_report(pr, num_th, aos, codes, mo, metric) for metric in metrics]

@@ -741,7 +741,7 @@ def do_train(cfg, distributed, model, data_loader, data_loaders_val, optimizer, 
             import os
             for name, loader in zip(cfg.DATASETS.TEST, data_loaders_val):
                 inference(model, loader, dataset_name=name, device=cfg.MODEL.DEVICE, metrics=cfg.TEST.METRIC,
-                          output_folder=os.path.join(cfg.OUTPUT_DIR, "inference_{}".format(iteration), name))
+                          eval_on_device=bool(cfg.TEST.EVAL_ON_DEVICE), output_folder=os.path.join(cfg.OUTPUT_DIR, "inference_{}".format(iteration), name))
             model.train()
             comm.synchronize()
     if graphed is not None:

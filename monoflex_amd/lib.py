@@ -245,6 +245,8 @@ SYMBOLS = {
     "mfx_kitti_eval_match_pass1": (_I, [ctypes.POINTER(KittiEvalDesc), _P]),
     "mfx_kitti_eval_thresholds": (_I, [ctypes.POINTER(KittiEvalDesc), _P, _P]),
     "mfx_kitti_eval_match_pass2": (_I, [ctypes.POINTER(KittiEvalDesc), _P]),
+    "mfx_kitti_eval_pack_count": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "mfx_kitti_eval_pack_rows": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "mfx_decode_boxes": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P]),
     "mfx_decode_boxes_mode": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _I, _P, _P, _P, _P]),
     "mfx_decode_boxes_cfg": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, ctypes.POINTER(DecodeCfg), _P, _P, _P, _P, _P]),
